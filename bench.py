@@ -13,18 +13,30 @@ its parent finished; later ready boxes go first; `--in-order` disables this): ea
 nep_lp_advance): a slot whose LP finishes takes the next box at once.  A node starts from its parent's
 final PDHG state when a slot still holds it (slots are refilled oldest-finished first; finished parents
 with open children are parked, `--park` slots), else from the root's, with the PDHG primal weight banded around
-8 x the model's cold-start weight (`--omega-ref`, nep_lp_set_reference_weight).  The timed region
-streams the WHOLE recorded trace once (1026 node LPs at 512x256, seed 0) and drains it, whatever --steps says:
-one *step* is 1/K of the trace (ms_per_step = wall / K), so `value` does not depend on --steps / --warmup (the
-warmup streams the first W x --batch boxes on a stream of its own, untimed).  A node counts only if the engine
+8 x the model's cold-start weight (`--omega-ref`, nep_lp_set_reference_weight).  One *step* is
+1/12 of the recorded trace (TRACE_STEPS; 85 or 86 of the 1026 node LPs at 512x256, seed 0): the timed region
+streams the first `--steps` twelfths of the trace and drains them, so the default `--steps 12` replays the WHOLE
+trace once and more steps start it again from its first box (ms_per_step = wall / steps); the warmup streams the
+first `--warmup` twelfths on a stream of its own, untimed.  A node counts only if the engine
 certifies it: repaired primal objective - Lagrangian bound <= tol*max(1,|bound|) and every row residual <= tol
 (DESIGN.md §4); nodes that stop at `--max-iters` keep a valid bound and are reported, not counted.  The root LP
 is solved before the timed region (its seconds are `lp.root_seconds`); the instance lives on the device before
-the timer starts; node bounds are uploaded inside it, as the B&B host does per node.  Secondary figures in the
-same JSON: `product_node_lp_per_s` (the product search's own node-LP rates), `native_replay` (the trace's first
-boxes on the models the product ran them on), `children_stream` (root children with `--fix` random c-fixings,
-the round-1..3 workload), `bnb` (the product search itself) and `alibaba_flows` (the reference's three Alibaba
-requests end to end beside its published processing_time).
+the timer starts; node bounds are uploaded inside it, as the B&B host does per node.
+
+Plain and `--full` runs.  A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the
+JSON line; the `x_pass` roofline figures come from launches sampled inside the timed steps.  `--full` adds the
+secondary figures to the same JSON (null in a plain run): `product_node_lp_per_s` (the product search's own
+node-LP rates), `native_replay` (the trace's first boxes on the models the product ran them on),
+`children_stream` (root children with `--fix` random c-fixings, the round-1..3 workload), `bnb` (the product
+search itself), `alibaba_flows` (the reference's three Alibaba requests end to end beside its published
+processing_time) and `cpu_baseline`.
+
+`--dump-outputs DIR`.  After the timed steps rank 0 writes what the engine returned for the node LPs of the LAST
+timed step — nep_lp_advance's per-LP results, in the order the stream takes the boxes (not completion order) — as
+float64 arrays DIR/<name>.npy: `entry` (position in the stream), `status`, `obj` (the Lagrangian bound),
+`primal_obj`, `iters`; values that are not finite (an LP presolve proves infeasible has no objective) are written
+as 0, `status` tells them apart.  The instance, the trace and every seed are fixed by the arguments, so two builds
+run with the same arguments solve the same LPs.
 
 Multi-GPU.  `--gpus N` > 1 without a launcher environment starts N rank processes itself
 (torch.distributed.run, one rank per GPU, 127.0.0.1 rendezvous) before anything touches the GPU; under a
@@ -58,16 +70,32 @@ for _p in (PKG, REPO):
         sys.path.insert(0, _p)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E peak (MI355X_MICROARCH.md "HBM")
+TRACE_STEPS = 12               # the recorded trace is this many steps long (one step = 1/12 of its node LPs)
+
+
+def replay_boxes(n_lps, steps):
+    """Node LPs in the first `steps` steps of a replay of a recorded trace of `n_lps` node LPs: step k covers the
+    trace's entries [k L / 12, (k + 1) L / 12); past its end the trace starts again."""
+    return (steps // TRACE_STEPS) * n_lps + (steps % TRACE_STEPS) * n_lps // TRACE_STEPS
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=12)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=12,
+                    help="timed steps: twelfths of the recorded trace (replay; 12 = the whole trace once) or "
+                         "--batch root children each (children stream)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before the timed ones")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary sections (native-model replay, children stream, "
+                         "product B&B, Alibaba flows, CPU baseline); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the engine's results for the node LPs of the last timed step as DIR/<name>.npy "
+                         "(float64: entry, status, obj, primal_obj, iters)")
     ap.add_argument("--nodes", type=int, default=512)
     ap.add_argument("--functions", type=int, default=256)
-    ap.add_argument("--batch", type=int, default=32, help="node LPs in flight per GPU (= node LPs per step)")
+    ap.add_argument("--batch", type=int, default=32,
+                    help="node LPs in flight per GPU (children stream: = node LPs per step)")
     ap.add_argument("--fix", type=int, default=2, help="c[f,j] fixings per node LP")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tol", type=float, default=1e-6)
@@ -110,7 +138,7 @@ def parse(argv=None):
                          "bnb_trace_<N>x<F>_s<seed>.json.gz) or root children with --fix random fixings; auto: "
                          "replay when the trace exists")
     ap.add_argument("--native-steps", type=int, default=6,
-                    help="with the replay stream: steps of the native-model replay timed after it (each recorded "
+                    help="--full with the replay stream: steps of the native-model replay timed after it (each recorded "
                          "box on the model the product ran it on; 0 = skip)")
     ap.add_argument("--park", type=int, default=1024,
                     help="replay: slots per model beyond --batch that keep finished nodes' states while their children "
@@ -121,14 +149,14 @@ def parse(argv=None):
                     help="replay: a node whose parent's state is gone starts from its closest resident ancestor's "
                          "(default: the root's, as the product B&B does)")
     ap.add_argument("--children-steps", type=int, default=24,
-                    help="with the replay stream: steps of the children stream timed after it (secondary figure)")
+                    help="--full with the replay stream: steps of the children stream timed after it (secondary figure)")
     ap.add_argument("--cpu-budget", type=float, default=150.0,
-                    help="seconds for the CPU baseline (0 = skip); the bench-size attempt gets what the fit leaves, "
+                    help="--full: seconds for the CPU baseline (0 = skip); the bench-size attempt gets what the fit leaves, "
                          ">= 30 s")
     ap.add_argument("--cpu-workers", type=int, default=0,
                     help="CPU baseline worker processes (0: the host's per-GPU share of its cores, cpu_baseline_workers)")
     ap.add_argument("--bnb-seconds", type=float, default=20.0,
-                    help="time limit of the product branch-and-bound section (0 = skip)")
+                    help="--full: time limit of the product branch-and-bound section (0 = skip)")
     ap.add_argument("--bnb-sizes", default="256x128:20,512x256:60",
                     help="instances of the product B&B section (BASELINE configs 3 and 4), NxF[:seconds] "
                          "comma-separated (seconds: that instance's time limit, default --bnb-seconds)")
@@ -138,7 +166,7 @@ def parse(argv=None):
     ap.add_argument("--dump", default=None, help="write per-node-LP records of the replay (kind, depth, warm source, "
                     "status, iterations, final diagnostics of the uncertified) to this JSON file")
     ap.add_argument("--alibaba-seconds", type=float, default=120.0,
-                    help="alibaba_flows section: the reference's three Alibaba 100x25 requests through core.request "
+                    help="--full, alibaba_flows section: the reference's three Alibaba 100x25 requests through core.request "
                          "(main.py's route body), each B&B step limited to this many seconds (a safety bound: they end "
                          "OPTIMAL well within it); 0 = skip")
     ap.add_argument("--traffic", default=os.path.join(REPO, "profiles", "traffic.json"))
@@ -424,8 +452,9 @@ class ReplayStream:
     `batch` slots per model; a node starts from its parent's final PDHG state when a slot of its model still
     holds it (slots are refilled oldest-finished first, as the B&B does; the recorded run's own slot reuse
     is not replayed), else from that model's root.  The
-    two roots (depth-0 entries) were solved before the timed region and are skipped.  With `world` ranks,
-    rank r takes entries r, r + world, ... (the trace repeated as often as the steps need)."""
+    two roots (depth-0 entries) were solved before the timed region and are skipped.  The trace is repeated
+    as often as the steps need (a repetition's nodes warm-start only from their own repetition); `drain(n)`
+    takes exactly the next n entries.  `seq` holds each completed node's position in that sequence."""
 
     def __init__(self, models, a, rank, world, trace, native=False):
         from collections import Counter, OrderedDict
@@ -433,9 +462,12 @@ class ReplayStream:
         self.lps = [e for e in trace["lps"] if e["parent"] is not None]
         self.parent_of = {e["id"]: e["parent"] for e in trace["lps"]}
         self.ancestors = getattr(a, "warm_ancestors", False)
-        self.pos = 0
+        self.index_of = {e["id"]: i for i, e in enumerate(self.lps)}
+        self.pos = 0            # entries taken from the sequence (submitted or deferred)
+        self.limit = None       # drain(): entries of the sequence this stream may take (None: no bound)
         self.counter = 0
         self.done = []          # (status, obj, primal_obj, iters) per completed node
+        self.seq = []           # position in the replayed sequence per completed node
         self.kinds = []         # (model, kind) per completed node
         self.depth = []         # (depth, warm from parent) per completed node
         self.where = {}         # (model, node key) -> slot holding its final state
@@ -460,11 +492,12 @@ class ReplayStream:
         self.in_order = bool(getattr(a, "in_order", False))
 
     def peek_entry(self):
-        """(repetition, entry) this rank replays next: the trace's entries in recorded order, once (None at its
-        end)."""
-        if self.pos >= len(self.lps):
+        """(repetition, entry) this rank replays next: the trace's entries in recorded order, the trace again after
+        its end (None once `limit` entries were taken)."""
+        if not self.lps or (self.limit is not None and self.pos >= self.limit):
             return None
-        return 0, self.lps[self.pos]
+        rep, i = divmod(self.pos, len(self.lps))
+        return rep, self.lps[i]
 
     def next_entry(self):
         out = self.peek_entry()
@@ -576,6 +609,7 @@ class ReplayStream:
                           warm_omega_floor=wf, warm_omega_cap=wc, polish_after=getattr(a, "polish_after", 0.0), **kw)
             if int(st[0]) == LP_INFEASIBLE:
                 self.done.append((LP_INFEASIBLE, float("inf"), float("nan"), 0))
+                self.seq.append(rep * len(self.lps) + self.index_of[e["id"]])
                 self.kinds.append((name, e["kind"]))
                 self.depth.append((e["depth"], warm_parent))
                 self.free[name].append(slot)
@@ -596,6 +630,7 @@ class ReplayStream:
                     self.done.append((int(r["status"][i]), float(r["obj"][i]), float(r["primal_obj"][i]),
                                       int(r["iters"][i])))
                     key, kind, depth, wp = self.running.pop((name, slot))
+                    self.seq.append(key[0] * len(self.lps) + self.index_of[key[1]])
                     if getattr(self.a, "dump", None):
                         st_ = int(r["status"][i])
                         rec = {"id": key[1], "kind": kind, "depth": depth, "warm_parent": wp, "status": st_,
@@ -646,6 +681,8 @@ class NodeStream:
         self.m, self.root, self.a, self.rank = m, root, a, rank
         self.counter = 0
         self.done = []          # (status, obj, primal_obj, iters) per completed node
+        self.seq = []           # position in the stream per completed node
+        self.slot_seq = {}      # slot -> position of the node iterating in it
 
     def _refill(self, slots):
         """Submit the next nodes into the free `slots` (one nep_lp_submit call); stops once `limit`
@@ -660,6 +697,7 @@ class NodeStream:
             lbs, ubs = [], []
             for slot in take:
                 seed = (a.seed * 1000003 + self.rank) * 7919 + self.counter
+                self.slot_seq[slot] = self.counter
                 self.counter += 1
                 lb, ub = node_bounds(self.m.n_int, a.functions, a.nodes, 1, a.fix, seed)
                 lbs.append(lb[0])
@@ -673,6 +711,7 @@ class NodeStream:
             for slot, code in zip(take, st):
                 if int(code) == LP_INFEASIBLE:
                     self.done.append((LP_INFEASIBLE, float("inf"), float("nan"), 0))
+                    self.seq.append(self.slot_seq.pop(slot))
                     free.append(slot)
 
     def drain(self, n):
@@ -684,7 +723,23 @@ class NodeStream:
             for i in range(len(r["slots"])):
                 self.done.append((int(r["status"][i]), float(r["obj"][i]), float(r["primal_obj"][i]),
                                   int(r["iters"][i])))
+                self.seq.append(self.slot_seq.pop(int(r["slots"][i])))
             self._refill(r["slots"].tolist())
+
+
+def dump_outputs(path, stream, lo, hi):
+    """--dump-outputs: the engine's results for the node LPs at positions [lo, hi) of `stream` (the last timed
+    step), ordered by position, as float64 arrays path/<name>.npy.  Values that are not finite are written as 0
+    (`status` tells such LPs apart)."""
+    import numpy as np
+    rows = sorted((q, r) for q, r in zip(stream.seq, stream.done) if lo <= q < hi)
+    os.makedirs(path, exist_ok=True)
+    cols = {"entry": [q - lo for q, _ in rows], "status": [r[0] for _, r in rows], "obj": [r[1] for _, r in rows],
+            "primal_obj": [r[2] for _, r in rows], "iters": [r[3] for _, r in rows]}
+    for name, v in cols.items():
+        np.save(os.path.join(path, name + ".npy"),
+                np.nan_to_num(np.asarray(v, np.float64), nan=0.0, posinf=0.0, neginf=0.0))
+    log(f"--dump-outputs: {len(rows)} node LPs of the last step written to {path}")
 
 
 def _free_port():
@@ -736,6 +791,8 @@ def _probe_ranks(a, rank, world):
 
 def main():
     a = parse()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
     rank, world, local = rank_world(a)
@@ -802,7 +859,7 @@ def main():
         with gzip.open(trace_path(a, seed), "rt") as fh:
             trace = json.load(fh)
         stream = ReplayStream({"leaf": (m, root)}, a, rank, world, trace)
-        if a.native_steps > 0:
+        if a.full and a.native_steps > 0:
             # the facility relaxation (the product's bound model) and its root, stopped as the product's is:
             # bound converged (bound_res 1e-2, gap_tol 1e-4) or the root budget (core/engine/bnb.py _submit)
             from core.engine.lp import RELAX_FACILITY
@@ -878,16 +935,23 @@ def main():
                 "gmax": gmax, "first_check_certified": int(n_first), "resolved": int(n_res), "iters_p50_p90_max": iq,
                 "util": util, "stats": st, "warm_split_rank0": split}
 
+    def boxes(steps):
+        """Node LPs of the first `steps` steps of the timed stream."""
+        return replay_boxes(len(stream.lps), steps) if kind == "replay" else steps * B
+
     if a.warmup > 0:
-        # untimed: the first W x B boxes (replay: on a stream of their own — the timed region then replays the
-        # whole trace from its start, so `value` does not depend on --steps / --warmup)
+        # untimed: the first W steps (replay: on a stream of their own — the timed region then replays the
+        # trace from its start, so the timed LPs do not depend on --warmup)
         ws = ReplayStream({"leaf": (m, root)}, a, rank, world, trace) if kind == "replay" else stream
-        ws.drain(a.warmup * B)
+        ws.drain(boxes(a.warmup))
         log(f"rank {rank}: warmup: {len(ws.done)} node LPs completed")
-    prim = timed(stream, a.steps, kind, count=len(stream.lps) if kind == "replay" else None)
+    first = stream.counter
+    prim = timed(stream, a.steps, kind, count=boxes(a.steps))
     if a.dump and rank == 0 and getattr(stream, "records", None) is not None:
         with open(a.dump, "w") as fh:
             json.dump(stream.records, fh)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, stream, first + boxes(a.steps - 1), first + boxes(a.steps))
     st = prim["stats"]
     wall, n_ok, n_it, gmax, n_done = prim["wall"], prim["certified"], prim["iterations"], prim["gmax"], prim["completed"]
     iq, util = prim["iters_p50_p90_max"], prim["util"]
@@ -910,7 +974,7 @@ def main():
                   "note": "resolved = certified + infeasible + cutoff + bound-converged (LP_BOUND); branching "
                           "nodes that end at their 1024-iteration budget keep a valid bound but are not counted"}
         bm.close()
-    if kind == "replay" and a.children_steps > 0:
+    if a.full and kind == "replay" and a.children_steps > 0:
         # the secondary figure: the round-1..3 stream of root children with 2 random c-fixings each
         cs = NodeStream(m, root, a, rank)
         sec = timed(cs, a.children_steps, "children")
@@ -921,7 +985,7 @@ def main():
     m.close()
     # the product's own B&B (every rank takes part: the sharded search when world > 1)
     bnb = None
-    if a.bnb_seconds > 0:
+    if a.full and a.bnb_seconds > 0:
         bnb = []
         for size in a.bnb_sizes.split(","):
             size, _, secs = size.partition(":")
@@ -952,9 +1016,9 @@ def main():
             per_lp_iter = t["bytes_per_launch"] / max(1, t.get("lps_per_launch", 1))
             traffic = per_lp_iter * lps_per_launch
             traffic_ratio = per_lp_iter / per_lp
-    flows = alibaba_flows(a) if (world == 1 and a.alibaba_seconds > 0) else None
+    flows = alibaba_flows(a) if (a.full and world == 1 and a.alibaba_seconds > 0) else None
     cpu = None
-    if world == 1 and a.cpu_budget > 0:
+    if a.full and world == 1 and a.cpu_budget > 0:
         cpu = cpu_baseline(N, F, a.seed, a.fix, a.cpu_budget, a.cpu_workers)
     out = {
         "metric": "LP-relaxations/sec + objective gap vs reference, 512-node×256-function",
@@ -963,6 +1027,7 @@ def main():
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": wall / a.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -974,13 +1039,13 @@ def main():
                    "routing_entries_P": P,
                    "parallelism": (f"bnb-subtrees x{world}" if kind != "replay" else
                                    ("one recorded B&B" if world == 1 else f"one recorded B&B per GPU x{world}")),
-                   "timed_lps_per_rank": (len(stream.lps) if kind == "replay" else a.steps * B),
+                   "timed_lps_per_rank": boxes(a.steps),
                    "instance_seed_rank0": seed,
                    "workload_note": ("value = certified LP relaxations of the REFERENCE model (the LP SCIP solves at "
                                      "each node) at the boxes the product's own 512x256 B&B submitted in 60 s "
-                                     "(tests/golden/bnb_trace_512x256_s<seed>.json.gz), the whole trace once per "
-                                     "rank in recorded order (a box waits for its parent's LP; finished parents "
-                                     "park their state, --park slots); one step = 1/K of the trace.  The product "
+                                     "(tests/golden/bnb_trace_512x256_s<seed>.json.gz), its first --steps twelfths "
+                                     "per rank (12 steps: the whole trace once) in recorded order (a box waits for "
+                                     "its parent's LP; finished parents park their state, --park slots).  The product "
                                      "search's own node-LP rate (branching nodes on the facility relaxation, "
                                      "budgets, stops) is `product_node_lp_per_s`"
                                      if kind == "replay" else "root children with random c-fixings")},

@@ -123,3 +123,69 @@ def test_replay_parks_parent_states(name):
         out[park] = s
     assert out[8].warm_parent >= out[0].warm_parent
     assert sorted(r[1] for r in out[8].done) == sorted(r[1] for r in out[0].done)
+
+
+class _StubLP:
+    """Node-LP backend without a solver: a submitted LP finishes at the second advance after it (so parents are
+    still iterating when their children come up), its value the index of the variable its box fixes."""
+
+    def __init__(self, n_int):
+        self.n_int = n_int
+        self.queue = []
+
+    def copy_state(self, src, dst):
+        pass
+
+    def submit(self, slots, lb, ub, **kw):
+        for s, row in zip(slots, lb):
+            self.queue.append([int(s), float(np.argmax(np.isfinite(row))), 2])
+        return np.ones(len(slots), np.int32)
+
+    def active(self):
+        return len(self.queue)
+
+    def advance(self, min_done):
+        for q in self.queue:
+            q[2] -= 1
+        out = [q for q in self.queue if q[2] <= 0]
+        self.queue = [q for q in self.queue if q[2] > 0]
+        k = len(out)
+        return {"slots": np.array([q[0] for q in out], np.int32), "obj": np.array([q[1] for q in out]),
+                "primal_obj": np.array([q[1] for q in out]), "status": np.zeros(k, np.int32),
+                "iters": np.full(k, 7, np.int64)}
+
+
+def test_replay_steps_take_exact_prefixes_and_wrap(tmp_path):
+    """--steps: K steps are the first K twelfths of the trace (12: the whole trace once, more: the trace again),
+    whatever order the LPs finish in; --dump-outputs writes the last step's results in stream order."""
+    import bench
+    L = 1026
+    assert bench.replay_boxes(L, 12) == L and bench.replay_boxes(L, 0) == 0
+    assert bench.replay_boxes(L, 1) == 85 and bench.replay_boxes(L, 13) == L + 85
+    assert all(bench.replay_boxes(L, k + 1) - bench.replay_boxes(L, k) in (85, 86) for k in range(40))
+    F, N = 2, 3
+    n_int = F * N + N
+    # a root, then a chain with side branches: entry i's parent is entry i - 1 or i - 2
+    lps = [{"id": 100, "parent": None, "kind": "node", "model": "leaf", "depth": 0, "fix": ([], [])}]
+    for i in range(30):
+        lps.append({"id": 101 + i, "parent": 100 + max(0, i - (i % 2)), "kind": "node", "model": "leaf",
+                    "depth": i + 1, "fix": ([i % n_int], [1.0])})
+    a = types.SimpleNamespace(batch=3, tol=1e-6, max_iters=64, check_every=12, warm_omega_floor=0.0,
+                              functions=F, nodes=N, park=4)
+    s = bench.ReplayStream({"leaf": (_StubLP(n_int), 7)}, a, 0, 1, {"lps": lps})
+    n5 = bench.replay_boxes(30, 5)
+    s.drain(n5)
+    assert sorted(s.seq) == list(range(n5)) and len(s.done) == n5 and not s.deferred
+    n17 = bench.replay_boxes(30, 17)
+    s.drain(n17 - n5)
+    assert sorted(s.seq) == list(range(n17)) and n17 > 30
+    assert s.seq != sorted(s.seq) or a.batch == 1      # (completion order is not stream order)
+    lo = bench.replay_boxes(30, 16)
+    s.done[s.seq.index(lo)] = (2, float("inf"), float("nan"), 0)
+    bench.dump_outputs(str(tmp_path / "out"), s, lo, n17)
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in ("entry", "status", "obj", "primal_obj", "iters")}
+    assert all(v.dtype == np.float64 and v.shape == (n17 - lo,) and np.isfinite(v).all() for v in got.values())
+    assert got["entry"].tolist() == list(range(n17 - lo))
+    assert got["status"][0] == 2 and got["obj"][0] == 0.0 and got["primal_obj"][0] == 0.0
+    assert got["obj"][1:].tolist() == [float(((lo + 1 + k) % 30) % n_int) for k in range(n17 - lo - 1)]
+    assert got["iters"][1:].tolist() == [7.0] * (n17 - lo - 1)

@@ -7,8 +7,10 @@
 #   tests          python -m pytest tests -m gpu (all GPU tests, -x, per-test timeout)
 #   tests:<files>  the GPU tests of the given comma-separated test files only
 #   smoke          __graft_entry__.smoke()
-#   bench          python bench.py (defaults: CPU baseline + product B&B sections included)
-#   bench:<args>   python bench.py <args, comma-separated> (e.g. bench:--seed,1,--cpu-budget,0) -> bench_args<k>.json
+#   bench          python bench.py --full (the headline replay, then the secondary sections: native replay, children
+#                  stream, product B&B, Alibaba flows, CPU baseline)
+#   bench:<args>   python bench.py <args, comma-separated> (e.g. bench:--seed,1 for a plain run of the headline
+#                  replay alone, bench:--full,--cpu-budget,0) -> bench_args<k>.json
 #   env:<VAR>=<v>  export a variable for the following steps (e.g. env:NEPTUNE_LP_LIB=lib/variants/...); unenv:<VAR>
 #   profile        rocprofv3 --kernel-trace --stats over the bench's timed replay -> kernel_stats_by_slots.csv
 #   traffic        separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over tools/traffic.py -> traffic.json
@@ -37,13 +39,13 @@ for r in "$@"; do
     tests) step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     tests:*) a=${r#tests:}; step pytest_sel 900 python -u -m pytest ${a//,/ } -m gpu -v -s --timeout 300 --timeout-method thread ;;
     smoke) step smoke 240 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python -u bench.py ; grep "^{" "$O/bench.log" | tail -1 > "$O/bench.json" ;;
+    bench) step bench 600 python -u bench.py --full ; grep "^{" "$O/bench.log" | tail -1 > "$O/bench.json" ;;
     bench:*) a=${r#bench:}; nb=$((nb + 1)); step bench_args$nb 600 python -u bench.py ${a//,/ }
       grep "^{" "$O/bench_args$nb.log" | tail -1 > "$O/bench_args$nb.json" ;;
     env:*) export "${r#env:}"; echo "== export ${r#env:}" ;;
     unenv:*) unset "${r#unenv:}"; echo "== unset ${r#unenv:}" ;;
     profile)
-      step profile 400 rocprofv3 --kernel-trace --stats -d /tmp/prof -o run -- python3 bench.py --steps 8 --cpu-budget 0 --bnb-seconds 0 --alibaba-seconds 0 --native-steps 0 --children-steps 0
+      step profile 400 rocprofv3 --kernel-trace --stats -d /tmp/prof -o run -- python3 bench.py --steps 12
       python3 tools/prof_summary.py /tmp/prof > "$O/kernel_stats_by_slots.csv"; cp /tmp/prof/*/*stats.csv "$O/" 2>/dev/null
       head -12 "$O/kernel_stats_by_slots.csv" | cut -c1-160 ;;
     traffic)
