@@ -443,16 +443,19 @@ __device__ __forceinline__ void st_x4(float *p, f32x4 v, bool nt) {
 
 // one routing row's operands: x̄ row, delay row D[src, :] (if the row has delay-weighted
 // coefficients) and the dense anchor row (if needed and the row's anchor is held dense)
+// `live`: bit q set = this lane loads its chunk q; a chunk not loaded reads as zeros, like one past NP (x_pass
+// clears the bits of chunks whose four destinations are all closed: memory holds +0 there, "Chunk elision")
 template <int CPL>
 __device__ __forceinline__ void load_row(const float *__restrict__ xrow, const float *__restrict__ drow,
                                          const float *__restrict__ arow, bool nd, bool na, bool nt, int lane,
-                                         int NP, float (&xo)[4 * CPL], float (&dout)[4 * CPL], float (&ao)[4 * CPL]) {
+                                         int NP, float (&xo)[4 * CPL], float (&dout)[4 * CPL], float (&ao)[4 * CPL],
+                                         uint32_t live = ~0u) {
 #pragma unroll
   for (int q = 0; q < CPL; ++q) {
     const int j0 = 4 * (lane + kWave * q);
     f32x4 a = {0.f, 0.f, 0.f, 0.f}, an = a;
     float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j0 < NP) {
+    if (j0 < NP && ((live >> q) & 1u)) {
       a = ld_x4(xrow + j0, nt);
       if (nd) d = ld4(drow + j0);
       if (na) an = ld_x4(arow + j0, nt);

@@ -785,6 +785,8 @@ int setup_device(Model &m, int max_batch, void *stream) {
     std::sscanf(e, "%lf,%lld", &v.polish_res, &b);
     v.polish_budget = b;
   }
+  v.xelide = 1;   // (0: the steady-state x_pass streams closed chunks too, for A/B; the results are the same bits)
+  if (const char *e = std::getenv("NEP_XPASS_ELIDE")) v.xelide = std::atoi(e) != 0;
   int rc;
   if ((rc = upload(m, &v.rows, m.rows))) return rc;
   if ((rc = upload(m, &v.frow, m.frow))) return rc;

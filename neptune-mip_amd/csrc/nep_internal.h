@@ -163,6 +163,9 @@ struct DeviceView {
   // bounds: a linear cost per (f, j); allocated / deallocated: one linear cost sT per unit of T = sum c - sum
   // old on an interval of T) — rows D1/D2/D3a/D3b are idle and D4's dual prices the row sum c in [L, U]
   int dred;
+  // steady-state x_pass skips the 16-byte chunks of a routing row whose four destinations are all closed
+  // (NEP_XPASS_ELIDE, read once at nep_model_create; 0: every row full width; nep_kernels.hip "Chunk elision")
+  int xelide;
   double sT, sum_old;
   DualLayout dl;
   IntLayout il;

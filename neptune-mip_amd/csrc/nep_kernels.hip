@@ -61,6 +61,18 @@
 #ifndef NEP_XPASS_PF_ANCHOR  // (0, default: the late prefetch leaves a dense anchor row to the row's top — 90 instead
 #define NEP_XPASS_PF_ANCHOR 0  //  of 96 VGPRs, 0.4955 vs 0.5044 ms per 32-slot launch; 1: prefetched with the rest)
 #endif
+// NEP_XPASS_ELIDE (1, default): the steady-state plain pass of rows of up to 512 destinations may skip the memory
+// traffic of closed 16-byte chunks ("Chunk elision" at x_pass); the model's run-time switch of the same name
+// (DeviceView::xelide, read at nep_model_create) turns it off per model.  0: the code is not compiled in.
+#ifndef NEP_XPASS_ELIDE
+#define NEP_XPASS_ELIDE 1
+#endif
+// NEP_XPASS_ELIDE_NT (build flag for A/B; 1, default: the launch's non-temporal policy holds for every function; 0: a
+// function whose mask leaves at most a quarter of its chunks open moves them with default-policy loads and stores,
+// so a leaf's few live lines could stay in the Infinity Cache between iterations; DESIGN.md §6 "Chunk elision")
+#ifndef NEP_XPASS_ELIDE_NT
+#define NEP_XPASS_ELIDE_NT 1
+#endif
 #ifndef NEP_XPASS_PF_CPL1    // (the prefetch for rows of <= 256 destinations too: 256x128 product search, 20 s:
 #define NEP_XPASS_PF_CPL1 1  //  9166 vs 8814 node LPs, the same incumbent and bound)
 #endif
@@ -207,6 +219,22 @@ __device__ __forceinline__ void loaded_shift(const DeviceView &v, int slot, int 
 // destinations per lane) gets the register budget of 4 / 2 waves per SIMD: held to 6 waves those variants spilled
 // 60 (CPL 4) to 280 (CPL 8) VGPRs per lane to scratch, and the 1024x512 lone root ran its TW 8 launches at 370 us
 // (DESIGN.md §6 "N > 512").
+// Chunk elision (steady-state variant only: !CHECK, !INIT, !FIRST, N <= 512): lane `lane` owns the 16-byte chunk
+// q of every row of f, destinations j0 .. j0 + 3 at j0 = 4 (lane + 64 q).  When the node's mask closes all four
+// ((mbits >> 4q) & 0xF == 0: a rounding leaf leaves ~6 of 128 chunks open) the lane issues neither the x, delay-row
+// and dense-anchor loads of that chunk, nor its store, nor the read-modify-write of its LDS column accumulators;
+// its registers hold 0.f as they do for j0 >= NP.  Same lanes, registers, DPP trees and values as the full-width
+// pass: only memory operations whose data is +0.f (or, for the delay row, multiplies an exact zero) are predicated.
+// INVARIANT this rests on: at a closed destination of an iterating slot, memory holds +0.f in x, and 0 in the
+// anchor (dense row and pairs alike).  Where it is established: the mask changes only in nep_lp_submit
+// (node_bounds_base / node_bounds_scatter), and every submit, cold or warm, runs the full-width INIT pass right
+// behind it, which stores x = the projection (`: 0.f` where the mask bit is off) and takes the anchor from it —
+// whatever a warm start copied in under a wider mask (nep_lp_copy_state(s) / nep_lp_copy_routing write idle slots
+// only, before their submit).  Where it is kept: every later pass stores lam (2 x̂ - x̄) + (1 - lam) anchor with
+// x̂ = x̄ = anchor = 0 there, i.e. +0.f (the FIRST pass with a restart takes the new anchor from x̄, zeros again;
+// polishing changes costs and duals, not the mask); the certificate's pooled_shift / loaded_shift pick deficits
+// (c's target > 0) and donors (flow > 0) among open destinations only, and the pooled row's write-back stores
+// (float)(0.0 / m) = +0.f elsewhere.  Nothing on the host writes x of an iterating slot (nep_round.cpp works on flows read back).
 // FIRST: the block's first iteration, the only one (with INIT) where a restart decided at the
 // certificate iteration takes effect and the anchor is rewritten; the steady-state variant carries
 // no restart code (fewer registers live).
@@ -214,7 +242,7 @@ template <int CPL, bool CHECK, bool INIT, bool FIRST, int TW>
 __global__ __launch_bounds__(kWave * TW) __attribute__((amdgpu_waves_per_eu(
     CHECK ? NEP_CHECK_WAVES : (TW == 16 ? 4 : (CPL >= 8 ? 2 : (CPL >= 4 ? 4 : ((NEP_XPASS_PREFETCH && !FIRST && (CPL == 2 || (NEP_XPASS_PF_CPL1 && CPL == 1))) ? NEP_XPASS_PF_WAVES : NEP_XPASS_WAVES)))), 8)))
 void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, int nslots, int nt_i) {
-  const bool nt = nt_i != 0;
+  bool nt = nt_i != 0;
   constexpr int E = 4 * CPL;
   extern __shared__ __attribute__((aligned(16))) float lds[];   // [2][TW][NP] accumulators + [2][NP] constants
   __shared__ double lds_s[TW][NTS + NBS];
@@ -327,6 +355,21 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
 #pragma unroll
   for (int e = 0; e < E; ++e) cnt_f += __popcll(__ballot((mbits >> e) & 1u));
 
+  // Chunk elision (see the header): bit q of `live` = this lane moves its chunk q of every row of f
+  constexpr bool kElide = NEP_XPASS_ELIDE && !CHECK && !INIT && !FIRST && CPL <= 2;
+  uint32_t live = ~0u;
+  if (kElide && v.xelide) {
+    live = 0;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) live |= (uint32_t)(((mbits >> (4 * q)) & 0xFu) != 0) << q;
+    if (!NEP_XPASS_ELIDE_NT) {   // (A/B: a function with at most a quarter of its chunks open keeps the default policy)
+      int nlive = 0;
+#pragma unroll
+      for (int q = 0; q < CPL; ++q) nlive += __popcll(__ballot((live >> q) & 1u));
+      if (16 * nlive <= NP) nt = false;
+    }
+  }
+
   double s_score = 0.0, s_pobj = 0.0, s_lagr = 0.0, s_lagr_r = 0.0, s_lagr0 = 0.0, s_move = 0.0, s_dist = 0.0;
   const double s_empty = (cnt_f == 0 && threadIdx.x == 0) ? (double)nrows : 0.0;
 
@@ -349,7 +392,7 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
     int qa = 0;
     if (need_anchor) qa = NEP_SPARSE_ANCHOR ? __builtin_amdgcn_readfirstlane(acnt[rn]) : kAnchorDense;
     load_row<CPL>(x + (int64_t)rn * NP, v.D + (int64_t)(q.src < 0 ? 0 : q.src) * NP, xa + (int64_t)rn * NP, row_nd(q),
-                  NEP_XPASS_PF_ANCHOR && need_anchor && qa > kAnchorK, nt, lane, NP, pfx, pfd, pfa);
+                  NEP_XPASS_PF_ANCHOR && need_anchor && qa > kAnchorK, nt, lane, NP, pfx, pfd, pfa, live);
     AnchorEnt qe{0, 0.f};
     if (need_anchor && qa <= kAnchorK && lane < qa) qe = aent[(int64_t)rn * kAnchorK + lane];
     pth = th_row[rn];
@@ -363,7 +406,7 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
     const RowInfo q = v.rows[r0 + wave];
     float dummy[E];
     load_row<CPL>(x + (int64_t)(r0 + wave) * NP, v.D + (int64_t)(q.src < 0 ? 0 : q.src) * NP, xa, row_nd(q), false, nt,
-                  lane, NP, pfx, pfd, dummy);
+                  lane, NP, pfx, pfd, dummy, live);
   }
   for (int rr = wave; rr < nrows; rr += TW) {
     const int r = r0 + rr;
@@ -379,7 +422,7 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
       for (int e = 0; e < E; ++e) { xc[e] = pfx[e]; dc[e] = pfd[e]; ac[e] = NEP_XPASS_PF_ANCHOR ? pfa[e] : 0.f; }
       if (!NEP_XPASS_PF_ANCHOR && need_anchor && acn > kAnchorK) {   // (A/B: the dense anchor loaded here instead)
         float d0[E], d1[E];
-        load_row<CPL>(xa + (int64_t)r * NP, v.D, xa + (int64_t)r * NP, false, false, nt, lane, NP, ac, d0, d1);
+        load_row<CPL>(xa + (int64_t)r * NP, v.D, xa + (int64_t)r * NP, false, false, nt, lane, NP, ac, d0, d1, live);
       }
     } else if (kPf) {
       // this row came in with the previous one; the next row's loads go out now, ahead of the projection
@@ -387,19 +430,19 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
       for (int e = 0; e < E; ++e) { xc[e] = pfx[e]; dc[e] = pfd[e]; ac[e] = 0.f; }
       if (need_anchor && acn > kAnchorK) {
         float d0[E], d1[E];
-        load_row<CPL>(xa + (int64_t)r * NP, v.D, xa + (int64_t)r * NP, false, false, nt, lane, NP, ac, d0, d1);
+        load_row<CPL>(xa + (int64_t)r * NP, v.D, xa + (int64_t)r * NP, false, false, nt, lane, NP, ac, d0, d1, live);
       }
       if (rr + TW < nrows) {
         const RowInfo q = v.rows[r + TW];
         float dummy[E];
         load_row<CPL>(x + (int64_t)(r + TW) * NP, v.D + (int64_t)(q.src < 0 ? 0 : q.src) * NP, xa, row_nd(q), false,
-                      nt, lane, NP, pfx, pfd, dummy);
+                      nt, lane, NP, pfx, pfd, dummy, live);
       }
     } else {
       // (default: no software prefetch of the next row — the registers it costs are worth more as occupancy,
       // 0.575 vs 0.591 ms per launch in round 1; other waves hide the latency)
       load_row<CPL>(x + (int64_t)r * NP, v.D + (int64_t)(ri.src < 0 ? 0 : ri.src) * NP, xa + (int64_t)r * NP, nd,
-                    need_anchor && acn > kAnchorK, nt, lane, NP, xc, dc, ac);
+                    need_anchor && acn > kAnchorK, nt, lane, NP, xc, dc, ac, live);
     }
     if (need_anchor && acn <= kAnchorK) {
       AnchorEnt ae{0, 0.f};
@@ -582,7 +625,7 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
 #pragma unroll
     for (int q = 0; q < CPL; ++q) {
       const int j0 = 4 * (lane + kWave * q);
-      if (j0 < NP) {
+      if (j0 < NP && ((live >> q) & 1u)) {   // (an elided chunk would store the +0 it holds)
         float o[4], rf[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -634,7 +677,7 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
 #pragma unroll
     for (int q = 0; q < CPL; ++q) {
       const int j0 = 4 * (lane + kWave * q);
-      if (j0 < NP) {
+      if (j0 < NP && ((live >> q) & 1u)) {   // (an elided chunk would add m * 0.f to sums that started at +0.f)
         const float *xq = xn + 4 * q;
         if (CHECK) {
           double2 *pd = reinterpret_cast<double2 *>(lSd + wave * NP + j0);
@@ -752,7 +795,9 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
 #pragma unroll
       for (int wv = 0; wv < TW && NEP_INLINE_REFLECT; ++wv) Sf += lR[wv * NP + j];
     } else {
-#pragma unroll
+      // (four waves' partials in flight at a time: with all 2 x 8 of TW 8 loaded at once the steady-state variant
+      // spilled a VGPR pair across this loop; the sums are taken in the same wave order)
+#pragma unroll 4
       for (int wv = 0; wv < TW; ++wv) {
         Sf += lS[wv * NP + j];
         Uf += lW[wv * NP + j];

@@ -11,7 +11,9 @@ Then (anywhere):
 node LPs on the first boxes of the bench's replay stream (tests/golden/bnb_trace_*.json.gz) warm from the
 root's state as the replay does, and runs 4 blocks of PDHG iterations: x_pass steady-state launches with all
 `batch` LPs active, as in the bench's timed region (`run cold`: no root solve, the nodes cold — the round-4
-workaround for the SIGSEGV of the first --pmc pass, DESIGN.md §6 "PMC pass crash").  `summarize` averages the counters
+workaround for the SIGSEGV of the first --pmc pass, DESIGN.md §6 "PMC pass crash"; `run leaf` / `run leaf-cold`: the
+first `batch` rounding-leaf boxes of the stream instead, a launch that carries leaf-type boxes only — DESIGN.md §6
+"Chunk elision"; the printed line then carries the HIP-event time of the sampled steady-state launches).  `summarize` averages the counters
 over the steady-state x_pass launches (x_pass<CPL, false, false>, full grid) and converts them:
 FETCH_SIZE and WRITE_SIZE are KiB (rocprofiler-sdk derived_counters.xml); FETCH_SIZE is doubled for
 wide streaming reads on gfx950 (MI355X_MICROARCH.md, HBM).
@@ -35,7 +37,8 @@ def run():
     a = bench.parse([])
     p = synthetic_payload(a.nodes, a.functions, seed=a.seed)
     d = data_to_solver_input(p, with_db=False)
-    cold = len(sys.argv) > 2 and sys.argv[2] == "cold"
+    mode = sys.argv[2] if len(sys.argv) > 2 else ""
+    cold, leaf = mode in ("cold", "leaf-cold"), mode in ("leaf", "leaf-cold")
     m = LPModel(d, "MinDelayAndUtilization", step=1, alpha=p["solver"]["args"]["alpha"], max_batch=a.batch + 1)
     root = a.batch
     if not cold:
@@ -43,7 +46,8 @@ def run():
     with gzip.open(bench.trace_path(a), "rt") as fh:
         trace = json.load(fh)
     rs = bench.ReplayStream({"leaf": (m, root)}, a, 0, 1, trace)
-    boxes = [rs._box(m, e) for e in rs.lps[:a.batch]]
+    lps = [e for e in rs.lps if e["kind"] == "leaf"] if leaf else rs.lps
+    boxes = [rs._box(m, e) for e in lps[:a.batch]]
     lb = np.array([b[0] for b in boxes])
     ub = np.array([b[1] for b in boxes])
     if not cold:
@@ -51,9 +55,14 @@ def run():
             m.copy_state(root, s)
     m.submit(np.arange(a.batch), lb, ub, tol=a.tol, max_iters=a.max_iters, check_every=a.check_every,
              warm_start=not cold)
-    for _ in range(4):
+    m.reset_stats()
+    for _ in range(12 if leaf else 4):
         m.advance(0)
-    print(json.dumps({"workload": bench.workload_name(a, "replay"), "active": m.active(), "P": m.info.x_entries}))
+    st = m.stats()
+    print(json.dumps({"workload": bench.workload_name(a, "replay"), "active": m.active(), "P": m.info.x_entries,
+                      "mode": mode, "x_pass_sampled": st["x_pass_sampled"],
+                      "x_pass_ms": st["x_pass_ms"] / max(1, st["x_pass_sampled"]),
+                      "lps_per_sampled_launch": st["x_pass_lp_iters"] / max(1, st["x_pass_sampled"])}))
     m.close()
 
 
