@@ -600,11 +600,7 @@ __global__ __launch_bounds__(kNodeThreads) void fac_node_pass(DeviceView v, cons
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-static size_t fac_lds_bytes(int tw, int NP, bool check) {
-  const int sw = check ? 2 : 1;
-  return (size_t)(sw * tw + tw + (check ? tw : 0) + 3) * NP * sizeof(float) + 3 * (size_t)NP * sizeof(double);
-}
-
+// (fac_lds_bytes, the dynamic LDS of one workgroup: nep_internal.h, shared with build()'s width check)
 template <int CPL, int TW>
 static hipError_t launch_fac_tw(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init,
                                 bool first, bool plain, int it, hipStream_t s) {
@@ -627,7 +623,7 @@ static int fac_tile_waves(const DeviceView &v, int nslots, bool check) {
   int tw = 4;
   while (tw < 16 && (int64_t)nslots * v.F * tw < 4096) tw *= 2;
   if (v.CPL >= 4 && tw > 8) tw = 8;   // (N > 512: 1024-thread workgroups cap a lane at 128 VGPRs, which spill)
-  while (tw > 4 && fac_lds_bytes(tw, v.NP, check) > 144 * 1024) tw /= 2;
+  while (tw > kMinTileWaves && fac_lds_bytes(tw, v.NP, check) > kLdsCap) tw /= 2;
   return tw;
 }
 
@@ -644,7 +640,7 @@ static hipError_t launch_fac_cpl(const DeviceView &v, const int32_t *slots, int 
 
 hipError_t launch_fac_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
                              bool plain, int it, hipStream_t s) {
-  if (fac_lds_bytes(4, v.NP, check) > 144 * 1024) return hipErrorInvalidValue;
+  if (fac_lds_bytes(kMinTileWaves, v.NP, check) > kLdsCap) return hipErrorInvalidValue;
   switch (v.CPL) {
     case 1: return launch_fac_cpl<1>(v, slots, nslots, check, init, first, plain, it, s);
     case 2: return launch_fac_cpl<2>(v, slots, nslots, check, init, first, plain, it, s);

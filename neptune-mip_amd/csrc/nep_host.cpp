@@ -265,7 +265,6 @@ int upload(Model &m, const T **dst, const std::vector<T> &src) {
 int build(Model &m, const nep_model_desc &d, bool host_power = true) {
   const int N = d.n_nodes, F = d.n_functions;
   if (N <= 0 || F <= 0) return fail(NEP_ERR_ARG, "n_nodes and n_functions must be positive");
-  if (N > 2048) return fail(NEP_ERR_ARG, "n_nodes > 2048 not supported by this build");
   if (d.variant < 0 || d.variant > 2) return fail(NEP_ERR_ARG, "bad variant");
   if (d.step < 1 || d.step > 3) return fail(NEP_ERR_ARG, "bad step");
   if (!d.delay || !d.workload || !d.core_per_req || !d.function_memory || !d.node_memory || !d.node_cores ||
@@ -287,6 +286,13 @@ int build(Model &m, const nep_model_desc &d, bool host_power = true) {
   m.eps = d.epsilon > 0 ? d.epsilon : 1e-6;
   m.sigma4 = d.step == NEP_STEP2_CREATE ? 1.0 : -1.0;
   m.NP = (N + 3) / 4 * 4;
+  // the widest rows whose certificate pass still fits a CU's LDS at the smallest tile (x_lds_bytes / fac_lds_bytes,
+  // nep_internal.h — the launchers' own formula): a wider model could iterate but never launch a certificate
+  if (const int np_max = max_padded_width(m.fac); m.NP > np_max)
+    return fail(NEP_ERR_ARG, "n_nodes = " + std::to_string(N) + " not supported by this build: the " +
+                                 (m.fac ? "facility" : "reference") + " relaxation's certificate pass holds rows of at most " +
+                                 std::to_string(np_max) + " destinations in LDS (largest supported n_nodes: " +
+                                 std::to_string(np_max) + ")");
   const int chunks = m.NP / 4;
   m.CPL = chunks <= 64 ? 1 : chunks <= 128 ? 2 : chunks <= 256 ? 4 : 8;
   m.W.assign(d.workload, d.workload + (size_t)F * N);
@@ -888,7 +894,9 @@ int setup_dense(Model &m, const nep_model_desc &d) {
     m.d_base_mask = const_cast<uint8_t *>(q);
   }
   if ((rc = dalloc(m, &m.d_sub_i, (size_t)3 * B + 1 + (size_t)B * v.sint))) return rc;
-  if ((rc = dalloc(m, &m.d_sub_d, (size_t)2 * B * v.sint))) return rc;
+  // (a submit stages at most one bound change per integer variable and LP — presolve_node appends an index once —
+  // i.e. 2 x nchg <= 2 B n_int doubles, and nep_lp_submit_ex two more per LP behind them: its budgets / bound stops)
+  if ((rc = dalloc(m, &m.d_sub_d, (size_t)2 * B * (v.sint + 1)))) return rc;
   HIPCHK(hipMemsetAsync(v.ctrl, 0, sizeof(Ctrl) * B, m.stream));
   HIPCHK(hipMemsetAsync(v.x, 0, sizeof(float) * B * v.sx, m.stream));
   HIPCHK(hipMemsetAsync(v.xa, 0, sizeof(float) * B * v.sx, m.stream));

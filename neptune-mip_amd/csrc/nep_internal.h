@@ -22,6 +22,7 @@
 // Static (shared by all slots): rows [R] (RowInfo), frow [F+1], D [N][NP] f32, cpr [F][NP] f32,
 // gamma [n_int], rho / lo / hi / rownorm [n_dual], cost_int [n_int].
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 // Build-time variants (A/B-measured on the MI355X):
@@ -36,6 +37,13 @@
 #endif
 #ifndef NEP_SPARSE_ANCHOR
 #define NEP_SPARSE_ANCHOR 1
+#endif
+// NEP_INLINE_REFLECT (build flag, default off until the whole GPU suite has run on it): the
+// C1/C2/D1/D2 duals take the reflected activity K(2ŵ - w) formed in x_pass instead of the tracked activities
+// kz / kza (48 B per (f, j) and LP-iteration less).  Here because it changes the certificate pass's LDS
+// (x_lds_bytes below), which the host's width check shares with the launchers.
+#ifndef NEP_INLINE_REFLECT
+#define NEP_INLINE_REFLECT 0
 #endif
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -79,6 +87,34 @@ struct AnchorEnt {
 };
 
 constexpr int kWave = 64;
+
+// Dynamic LDS of one x-pass workgroup of `tw` waves on rows of NP (padded) destinations, in bytes — the one
+// formula behind the launch size (launch_x_tw / launch_fac_tw), the choice of waves per workgroup (tile_waves /
+// fac_tile_waves) and the widths a model may have (build(), nep_host.cpp).
+//   reference relaxation (x_pass): per wave the column-sum and CPU-sum accumulators (fp32; fp64 on certificate
+//   iterations, plus the fp32 reflected sums of a NEP_INLINE_REFLECT build), the packed-dual constants lK / lC, and on
+//   certificate iterations their fp64 copies, the repaired prices and the pooled row's flow (4 x NP doubles)
+//   facility relaxation (fac_x_pass): see its LDS layout in nep_fac.hip
+// The certificate variants are held to kLdsCap: the 160 KiB of a CU less the kernels' static scalar partials
+// (lds_s, TW x (NTS + NBS) doubles: 1152 B at 4 waves) and headroom.  A workgroup has at least 4 waves, so a width
+// whose certificate pass exceeds the cap at 4 waves cannot launch: build() refuses it.
+constexpr size_t kLdsCap = 144 * 1024;
+constexpr int kMinTileWaves = 4;
+NEP_HD inline size_t x_lds_bytes(int tw, int NP, bool check) {
+  return (size_t)(2 * tw + 2) * NP * sizeof(float) +
+         (check ? (size_t)(NEP_INLINE_REFLECT ? 3 : 2) * tw * NP * sizeof(float) + 4 * (size_t)NP * sizeof(double) : 0);
+}
+NEP_HD inline size_t fac_lds_bytes(int tw, int NP, bool check) {
+  const int sw = check ? 2 : 1;
+  return (size_t)(sw * tw + tw + (check ? tw : 0) + 3) * NP * sizeof(float) + 3 * (size_t)NP * sizeof(double);
+}
+// the largest padded width NP (a multiple of 4) whose certificate pass fits the cap at kMinTileWaves
+inline int max_padded_width(bool fac) {
+  int np = 4;
+  while ((fac ? fac_lds_bytes(kMinTileWaves, np + 4, true) : x_lds_bytes(kMinTileWaves, np + 4, true)) <= kLdsCap) np += 4;
+  return np;
+}
+
 constexpr int64_t kOmegaTrained = 1024;  // warm_omega_cap applies when the parent lineage iterated this much
 constexpr double kPolishRes = 1e-3;        // polishing entry: primal residual at most this
 constexpr int64_t kPolishBudget = 512;     // polishing iterations before the LP goes back to its own objective
@@ -116,6 +152,8 @@ enum {
   NBS = BS_LKR0 + 6       //   repaired column prices (DESIGN.md §4 "Dual repair")
 };
 constexpr int kNLam = 6;
+static_assert(kLdsCap + 16 * (NTS + NBS) * sizeof(double) <= 160 * 1024,
+              "dynamic LDS cap + the widest tile's static scalar partials must fit a CU's 160 KiB");
 // BS_POBJ / BS_RES carry, on certificate iterations, the objective of the REPAIRED small variables and
 // the max violation of the rows at the repaired point (DESIGN.md §4 "Certificate").
 

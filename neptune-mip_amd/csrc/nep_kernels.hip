@@ -30,12 +30,7 @@
 #include "nep_internal.h"
 #include "nep_device.h"
 
-// NEP_INLINE_REFLECT (build flag, default off until the whole GPU suite has run on it):
-// the C1/C2/D1/D2 duals take the reflected activity K(2ŵ - w) formed in x_pass instead of the tracked
-// activities kz / kza (48 B per (f, j) and LP-iteration less)
-#ifndef NEP_INLINE_REFLECT
-#define NEP_INLINE_REFLECT 0
-#endif
+// (NEP_INLINE_REFLECT, the build flag of the inline reflection: nep_internal.h)
 // NEP_XPASS_PREFETCH: the plain x_pass (rows of up to 512 destinations) loads each wave's NEXT routing row into
 // registers while it works on the current one (5 waves per SIMD instead of 6).  1: the next row's x and delay row go
 // out before the projection — measured slower (0.575 vs 0.545 ms per 29-slot launch, round 6; round 1 likewise).
@@ -577,6 +572,11 @@ void x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int it, 
       // applying th64 to every masked entry moved entries across the fp32 support's edge); the final threshold
       // is always the one computed from the final support, whose entries outside stay 0
       double th64 = (double)theta;
+      // (the sentinel below reads as "no support yet" only while no lane can own all 32 entries of a support, i.e.
+      // while some lane has fewer than 32 open destinations: with every one of a CPL 8 lane's 32 open on every lane
+      // — N = 2048, full mask — the first pass would see ns == sup everywhere and keep the fp32 threshold.  build()
+      // admits NP <= max_padded_width() = 1416 (1228 with NEP_INLINE_REFLECT): a lane owns at most 6 chunks, 24
+      // destinations, so the case cannot occur)
       uint32_t sup = 0xffffffffu;
 #pragma unroll 1
       for (int it = 0; it < 4; ++it) {
@@ -1689,8 +1689,7 @@ template <int CPL, int TW>
 static hipError_t launch_x_tw(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init,
                               bool first, bool plain, int it, hipStream_t s) {
   dim3 grid(8 * ((v.F * nslots + 7) / 8)), block(kWave * TW);
-  const size_t lds = (size_t)(2 * TW + 2) * v.NP * sizeof(float) +
-                    (check ? (size_t)(NEP_INLINE_REFLECT ? 3 : 2) * TW * v.NP * sizeof(float) + 4 * v.NP * sizeof(double) : 0);
+  const size_t lds = x_lds_bytes(TW, v.NP, check);
   const int pl = plain ? 1 : 0;
   // non-temporal routing streams only when the iterating slots' x + anchor exceed ~160 MB (see ld_x4)
   const int nt = (double)nslots * 2.0 * (double)v.sx * sizeof(float) > 160e6 ? 1 : 0;
@@ -1715,8 +1714,7 @@ static int tile_waves(const DeviceView &v, int nslots, bool check) {
   int tw = 4;
   while (tw < 16 && (int64_t)nslots * v.F * tw < 4096) tw *= 2;
   if (v.CPL >= 8 && tw > 8) tw = 8;   // (N > 1024: 1024-thread workgroups cap a lane at 128 VGPRs, which spill)
-  while (check && tw > 4 && (size_t)((NEP_INLINE_REFLECT ? 5 : 4) * tw + 2) * v.NP * sizeof(float) + 4 * v.NP * sizeof(double) > 144 * 1024)
-    tw /= 2;
+  while (check && tw > kMinTileWaves && x_lds_bytes(tw, v.NP, true) > kLdsCap) tw /= 2;
   return tw;
 }
 
@@ -1739,6 +1737,8 @@ hipError_t launch_fac_node_pass(const DeviceView &v, const int32_t *slots, int n
 hipError_t launch_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
                          bool plain, int it, hipStream_t s) {
   if (v.fac) return launch_fac_x_pass(v, slots, nslots, check, init, first, plain, it, s);   // (nep_fac.hip)
+  // (build() admits no such width; a view from elsewhere fails here instead of at the launch)
+  if (x_lds_bytes(kMinTileWaves, v.NP, check) > kLdsCap) return hipErrorInvalidValue;
   switch (v.CPL) {
     case 1: return launch_x_cpl<1>(v, slots, nslots, check, init, first, plain, it, s);
     case 2: return launch_x_cpl<2>(v, slots, nslots, check, init, first, plain, it, s);

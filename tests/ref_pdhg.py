@@ -265,12 +265,21 @@ class RefModel:
                 out[r] = self.row_wsc[r] * D[self.row_src[r]]
         return out
 
+    def colsum(self, A):
+        """[F, N] sums of the rows A[r] of each function, added in row order (a function's rows are consecutive):
+        what np.add.at(S, row_f, A) gives, bit for bit, without its per-element dispatch."""
+        S = np.zeros((self.F, self.N))
+        if self.R:
+            starts = np.flatnonzero(np.r_[True, self.row_f[1:] != self.row_f[:-1]])
+            for a, b in zip(starts, np.r_[starts[1:], self.R]):
+                S[self.row_f[a]] = np.add.reduce(A[a:b], axis=0)
+        return S
+
     # K·[x, z] (unscaled) and Kᵀy (unscaled)
     def K(self, x, z):
         N, F = self.N, self.F
         y = np.zeros(self.n_dual)
-        S = np.zeros((F, N))
-        np.add.at(S, self.row_f, self.row_m[:, None] * x)
+        S = self.colsum(self.row_m[:, None] * x)
         y[self.o1:self.o1 + F * N] += S.ravel()
         y[self.o2:self.o2 + F * N] += S.ravel()
         y[self.o5:self.o5 + N] += (self.wc * x).sum(axis=0)
@@ -335,7 +344,155 @@ def proj_simplex_rows(V, mask):
     return out
 
 
-def solve(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, verbose=False, inline_reflect=False):
+def proj_simplex_rows_sorted(V, mask, return_theta=False):
+    """proj_simplex_rows with every row sorted at once: the same sort, running sums (in the same order) and
+    threshold per row, so the same values bit for bit (tests/test_abi.py) — the row loop costs ~0.1 ms a row."""
+    Vm = np.where(mask, V, -INF)
+    u = -np.sort(-Vm, axis=1)
+    with np.errstate(invalid="ignore"):
+        css = np.cumsum(u, axis=1)
+        k = np.arange(1, V.shape[1] + 1)
+        pos = u - (css - 1) / k > 0
+    cnt = mask.sum(axis=1)
+    rho = V.shape[1] - 1 - np.argmax(pos[:, ::-1], axis=1)
+    theta = (css[np.arange(V.shape[0]), rho] - 1) / (rho + 1)
+    out = np.where(mask, np.maximum(V - theta[:, None], 0), 0.0)
+    out[cnt == 0] = 0.0
+    return (out, np.where(cnt == 0, INF, theta)) if return_theta else out
+
+
+def _f32(a):
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _row_lagr(y, lo, hi):
+    with np.errstate(invalid="ignore"):
+        return np.where(y > 0, np.where(np.isfinite(lo), y * lo, -INF),
+                        np.where(y < 0, np.where(np.isfinite(hi), y * hi, -INF), 0.0))
+
+
+def _price_rc(b, s, M):
+    return b + M * np.minimum(s, 0.0) + np.maximum(s, 0.0)
+
+
+def _price_at(b, target, M):
+    d = target - b
+    return np.where(d < 0, d / M, d)
+
+
+def _repair_box(b, s0, z, lb, ub, M, eps, K):
+    """nep_device.h repair_box, elementwise: the re-priced big-M pair (s = y1 + y2, or t = y6 + y7) of a variable
+    on [lb, ub] with reduced cost price_rc(b, s) and iterate z."""
+    tol = 1e-7
+    inner = (z > lb + tol) & (z < ub - tol)
+    at0 = (z <= lb + tol) & (lb == 0.0)
+    p0 = _price_at(b, 0.0, M)
+    best = np.full(np.shape(b), -INF)
+    sb = np.array(s0, float, copy=True)
+    for s in (s0, np.zeros_like(b), p0, -b):
+        rc = _price_rc(b, s, M)
+        val = np.minimum(rc * lb, rc * ub) - eps * np.maximum(s, 0.0) - K * np.maximum(s - s0, 0.0)
+        take = val > best
+        best = np.where(take, val, best)
+        sb = np.where(take, s, sb)
+    return np.where(inner | at0, p0, sb)
+
+
+def engine_certificate(m, lb, ub, fmask, y, z, xn, zn, cost_x, cost_int, const, lag_plain):
+    """What the kernels' certificate iteration reports (nep_kernels.hip x_pass / node_pass / scalar_pass CHECK,
+    DESIGN.md §4 "Certificate", "Dual repair"), in fp64, for step 1 and the reduced step-2 block: the objective
+    and the largest violation at the REPAIRED point (c clamped onto [S / M, S + eps] and n onto [sum c / M,
+    sum c + eps] within their boxes, moved / allocated / deallocated the cheapest completion), the better of
+    the plain Lagrangian bound and the one at the repaired big-M prices, and the column deficits the pooled /
+    loaded shift would serve (c_target - eps - S: the mirror has no shift, so a caller asserts there are none).
+    y, z: the iterate the iteration starts from; xn, zn: its T output."""
+    if m.step2 and not m.dred:
+        raise NotImplementedError("engine_certificate: the full step-2 disruption block is not mirrored")
+    N, F, M, eps = m.N, m.F, m.M, m.eps
+    FN = F * N
+    oc = m.oc
+    S = m.colsum(m.row_m[:, None] * xn)
+    U = (m.wc * xn).sum(axis=0)
+    y1, y2 = y[m.o1:m.o1 + FN].reshape(F, N), y[m.o2:m.o2 + FN].reshape(F, N)
+    y3, y5 = y[m.o3:m.o3 + N], y[m.o5:m.o5 + N]
+    yS = y[m.oS] if m.step2 else 0.0
+    yD4 = y[m.oD4] if m.step2 else 0.0
+    lbc, ubc = lb[oc:oc + FN].reshape(F, N), ub[oc:oc + FN].reshape(F, N)
+    zc, cn = z[oc:oc + FN].reshape(F, N), zn[oc:oc + FN].reshape(F, N)
+    cc = m.cost_int[oc:oc + FN].reshape(F, N)          # (the reference's cost of c: 0 on step 2)
+    old = m.old.reshape(F, N)
+    # deficits the certificate's shifts would serve
+    tlo, thi = lbc, ubc
+    if m.step2:
+        tlo = np.maximum(lbc, old - ub[m.omt:m.omt + FN].reshape(F, N))
+        thi = np.minimum(ubc, old + ub[m.omf:m.omf + FN].reshape(F, N))
+    deficit = np.minimum(np.maximum(zc, tlo), thi) - eps - S
+    # repaired prices
+    ts = np.zeros(N)
+    lr = 0.0
+    if m.has_n:
+        on = m.on
+        bn = m.cost_int[on:on + N] - m.score_n_coef * yS
+        ts = _repair_box(bn, y[m.o6:m.o6 + N] + y[m.o7:m.o7 + N], z[on:on + N], lb[on:on + N], ub[on:on + N], M, eps,
+                         float(F))
+        rcn = _price_rc(bn, ts, M)
+        lr += (_row_lagr(np.minimum(ts, 0.0), m.lo[m.o6:m.o6 + N], m.hi[m.o6:m.o6 + N]) +
+               _row_lagr(np.maximum(ts, 0.0), m.lo[m.o7:m.o7 + N], m.hi[m.o7:m.o7 + N]) +
+               np.minimum(lb[on:on + N] * rcn, ub[on:on + N] * rcn)).sum()
+    b = cc - m.mem_f[:, None] * y3[None, :] - ts[None, :]
+    if m.dred:
+        b = b + cost_int[oc:oc + FN].reshape(F, N) - yD4
+    sr = _repair_box(b, y1 + y2, zc, lbc, ubc, M, eps, float(N))
+    rcr = _price_rc(b, sr, M)
+    lr += (np.minimum(lbc * rcr, ubc * rcr) - eps * np.maximum(sr, 0.0)).sum() + const
+    g0 = cost_x - m.wc * y5[None, :]
+    if m.step2:
+        g0 = g0 - m._score_coef(m.D32) * yS
+    lr += np.where(fmask[m.row_f], g0 - m.row_m[:, None] * sr[m.row_f], INF).min(axis=1).sum()
+    lr += (_row_lagr(y3, m.lo[m.o3:m.o3 + N], m.hi[m.o3:m.o3 + N]) +
+           _row_lagr(y5, m.lo[m.o5:m.o5 + N], m.hi[m.o5:m.o5 + N])).sum()
+    if m.dred:
+        lr += float(_row_lagr(np.float64(yS), m.lo[m.oS], m.hi[m.oS])) + \
+            float(_row_lagr(np.float64(yD4), m.lo[m.oD4], m.hi[m.oD4]))
+    lagr = max(lag_plain, lr)
+    # repaired point
+    loc, hic = np.maximum(lbc, S / M), np.minimum(ubc, S + eps)
+    if m.step2:
+        fits = np.maximum(loc, tlo) <= np.minimum(hic, thi)
+        loc, hic = np.where(fits, np.maximum(loc, tlo), loc), np.where(fits, np.minimum(hic, thi), hic)
+    cr = np.where(loc > hic, loc, np.minimum(np.maximum(cn, loc), hic))
+    res = max(0.0, float((loc - hic).max()))
+    pobj = (cost_x * xn).sum() + (cc * cr).sum()
+    viol = lambda a, lo, hi: np.maximum(np.maximum(lo - a, a - hi), 0.0)   # noqa: E731
+    res = max(res, float((viol((m.mem_f[:, None] * cr).sum(axis=0), m.lo[m.o3:m.o3 + N], m.hi[m.o3:m.o3 + N]) /
+                          m.rownorm[m.o3:m.o3 + N]).max()),
+              float((viol(U, m.lo[m.o5:m.o5 + N], m.hi[m.o5:m.o5 + N]) / m.rownorm[m.o5:m.o5 + N]).max()))
+    nr = np.zeros(N)
+    if m.has_n:
+        sumr = cr.sum(axis=0)
+        lon, hin = np.maximum(lb[on:on + N], sumr / M), np.minimum(ub[on:on + N], sumr + eps)
+        nr = np.where(lon > hin, lon, np.minimum(np.maximum(zn[on:on + N], lon), hin))
+        res = max(res, float((lon - hin).max()))
+        pobj += (m.cost_int[on:on + N] * nr).sum()
+    if m.step2:
+        lmf, lmt = lb[m.omf:m.omf + FN].reshape(F, N), lb[m.omt:m.omt + FN].reshape(F, N)
+        mfr, mtr = np.maximum(lmf, cr - old), np.maximum(lmt, old - cr)
+        res = max(res, float((mfr - ub[m.omf:m.omf + FN].reshape(F, N)).max()),
+                  float((mtr - ub[m.omt:m.omt + FN].reshape(F, N)).max()))
+        pobj += (m.cost_int[m.omf:m.omf + FN] * mfr.ravel()).sum() + (m.cost_int[m.omt:m.omt + FN] * mtr.ravel()).sum()
+        s = cr.sum() - m.old.sum()
+        A, Dm, Kk = min(ub[m.oa], -s), min(ub[m.od], s), m.sigma4 * (-s)
+        ar = max(lb[m.oa], A)
+        dr = max(lb[m.od], Kk - ar)
+        res = max(res, lb[m.oa] - A, dr - Dm)
+        pobj += m.cost_int[m.oa] * ar + m.cost_int[m.od] * dr
+        score_rep = (m._score_coef(m.D32) * xn).sum() + m.score_n_coef * nr.sum()
+        res = max(res, float(viol(score_rep, m.lo[m.oS], m.hi[m.oS]) / m.rownorm[m.oS]))
+    return dict(pobj=float(pobj), lagr=float(lagr), lagr_repaired=float(lr), res=float(res), deficit=deficit)
+
+
+def blocks(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, verbose=False, inline_reflect=False,
+           box=None, eta=None, omega0=None, rs_nec=0.8, fp32=False, engine=False):
     """Same algorithm as the kernels, fp64: blocks of `check_every` iterations; iteration 0 of a block
     is the certificate iteration (a plain PDHG step whose input dual is the previous block's plain
     output), restarts take effect at iteration 1, the last iteration is plain, the others are
@@ -343,22 +500,44 @@ def solve(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ver
     inline_reflect: form the dual step's reflected activity as K(2ŵ - w) from the primal points
     (what x_pass does for the per-(f, j) rows) instead of 2·Kŵ - kz with the tracked activity kz;
     the two are the same operator (K is linear).
-    Returns dict(status, obj, pobj, iters, x, z, y)."""
-    ok, lb, ub, fmask = m.presolve(lbi, ubi)
+    A generator: one record per certificate iteration, taken right after it — dict(k, status (None while the LP
+    iterates), obj, pobj, lag, res, x, z, y (copies of the iterate after that plain step), fpr, last_fpr, prev_fpr,
+    k_since (the restart test's operands), dz, dy, restart, omega).  solve() below runs it to its end.
+    To step beside the engine (tests/test_gpu_iterates.py): box = (lb, ub) the engine's presolved node box
+    (nep_debug_presolve) instead of the mirror's own presolve; eta / omega0 the engine's step size and initial primal
+    weight (its power iteration agrees with the mirror's to 1 % only); rs_nec the "necessary" restart factor
+    (nep_host.cpp runs 0.9; 0.8 here by default); engine=True adds record["cert"] = engine_certificate(...).
+    fp32=True rounds to float32 what the kernels hold in float32 — the routing iterate x, its anchor and the
+    projected x̂, the packed duals y1 + y2, cpr y5 and yS the x update reads (kty), tau and lambda in the x
+    update, the shifted point x - tau (wobj D - (m kx + w cy5 + wsc yS D)) evaluated term by term in float32
+    arithmetic as x_pass writes it (its terms reach tau |g| ~ 10^2 and cancel, so rounding only the result would
+    miss most of the noise), the simplex threshold of the plain iterations, and, outside certificate iterations,
+    the column sums and CPU sums the duals of C1/C2/C5 take — everything else stays fp64 as on the device: the
+    difference to the fp64 run measures the fp32 noise of the iteration itself (not the kernels' summation orders)."""
+    if box is None:
+        ok, lb, ub, fmask = m.presolve(lbi, ubi)
+    else:
+        lb, ub = np.array(box[0], float), np.array(box[1], float)
+        fmask = (ub[m.oc:m.oc + m.F * m.N] > 0).reshape(m.F, m.N)
+        ok = bool(fmask.any(axis=1).all()) and not np.any(lb > ub + 1e-12)
     if not ok:
-        return dict(status=2, obj=INF, pobj=np.nan, iters=0)
+        yield dict(status=2, obj=INF, pobj=np.nan, iters=0, k=0)
+        return
     mask = fmask[m.row_f]
     ce = check_every
+    r32 = _f32 if fp32 else (lambda a: a)
+    FN = m.F * m.N
     cost_int, const = m.cost_int, 0.0
     if m.dred:
         cost_int, const, m.lo[m.oD4], m.hi[m.oD4] = m.dred_terms(lb, ub)
-    x = proj_simplex_rows(np.zeros((m.R, m.N)), mask)
+    x = proj_simplex_rows_sorted(np.zeros((m.R, m.N)), mask)
+    x = r32(x)
     z = np.clip(np.zeros(m.n_int), lb, ub)
     y = np.zeros(m.n_dual)
     kz = m.K(x, z)
     xa, za, ya, kza = x.copy(), z.copy(), y.copy(), kz.copy()
-    omega, eta = m.omega0, m.eta
-    om_lo, om_hi = m.omega0 * 1e-5, m.omega0 * 1e5
+    omega, eta = (m.omega0 if omega0 is None else float(omega0)), (m.eta if eta is None else float(eta))
+    om_lo, om_hi = omega * 1e-5, omega * 1e5
     k = k_since = 0
     ks_base = -ce
     restart_pending = False
@@ -376,9 +555,35 @@ def solve(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ver
             gx, gz = m.KT(y)
             rcx = cost_x - gx
             rcz = cost_int - gz
-            xn = proj_simplex_rows(x - tau * rcx, mask)
+            if fp32:
+                # the x update reads the packed fp32 duals (kty) and an fp32 tau; the Lagrangian above keeps rcx
+                # and forms the shifted point in float32 arithmetic, term by term as x_pass writes it:
+                # v = x - tau (wobj D - (m kx + w cy5 + wsc yS D))
+                f4 = np.float32
+                y12 = (y[m.o1:m.o1 + FN] + y[m.o2:m.o2 + FN]).astype(f4).reshape(m.F, m.N)
+                cy5 = m.cpr32.astype(f4) * y[m.o5:m.o5 + m.N].astype(f4)[None, :]
+                Dr = np.where(m.row_src[:, None] >= 0, m.D32[np.maximum(m.row_src, 0)], 0.0).astype(f4)
+                gs = m.row_wsc.astype(f4) * f4(y[m.oS] if m.step2 else 0.0)
+                g = m.row_wobj.astype(f4)[:, None] * Dr - (m.row_m.astype(f4)[:, None] * y12[m.row_f] +
+                                                           m.row_w.astype(f4)[:, None] * cy5[m.row_f] +
+                                                           gs[:, None] * Dr)
+                vv = (x.astype(f4) - f4(tau) * g).astype(np.float64)
+                xn, theta = proj_simplex_rows_sorted(vv, mask, return_theta=True)
+                if not check:       # (plain iterations: an fp32 threshold; certificate ones refine it in fp64)
+                    xn = np.where(mask, np.maximum(vv - _f32(theta)[:, None], 0), 0.0)
+                xn = _f32(xn)
+            else:
+                xn = proj_simplex_rows_sorted(x - tau * rcx, mask)
             zn = np.clip(z - tau * m.gam ** 2 * rcz, lb, ub)
             act = m.K(xn, zn)
+            if fp32 and not check:
+                # outside certificate iterations the column sums S (C1/C2) and the per-function CPU sums (C5, times
+                # cpr) are fp32 accumulators
+                Sx, Ux = m.colsum(m.row_m[:, None] * xn), m.colsum(m.row_w[:, None] * xn)
+                dS = (_f32(Sx) - Sx).ravel()
+                act[m.o1:m.o1 + FN] += dS
+                act[m.o2:m.o2 + FN] += dS
+                act[m.o5:m.o5 + m.N] += _f32(_f32(Ux) * m.cpr32).sum(axis=0) - (m.wc * xn).sum(axis=0)
             s = sig * m.rho ** 2
             V = y - s * (m.K(2 * xn - x, 2 * zn - z) if inline_reflect else 2 * act - kz)
             with np.errstate(invalid="ignore"):
@@ -399,12 +604,17 @@ def solve(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ver
                 mvy = (((yn - y) / m.rho) ** 2).sum()
                 dsz = ((xn - xa) ** 2).sum() + (((zn - za) / m.gam) ** 2).sum()
                 dsy = (((yn - ya) / m.rho) ** 2).sum()
+                cert = engine_certificate(m, lb, ub, fmask, y, z, xn, zn, cost_x, cost_int, const, lag) if engine \
+                    else None
             if plain:
                 x, z, y, kz = xn, zn, yn, act
             else:
                 ks = ks_base + it
                 lam = (ks + 1.0) / (ks + 2.0)
-                x = lam * (2 * xn - x) + (1 - lam) * xa
+                if fp32:
+                    x = _f32(_f32(lam) * (2 * xn - x) + (1 - _f32(lam)) * xa)
+                else:
+                    x = lam * (2 * xn - x) + (1 - lam) * xa
                 z = lam * (2 * zn - z) + (1 - lam) * za
                 y = lam * (2 * yn - y) + (1 - lam) * ya
                 kz = lam * (2 * act - kz) + (1 - lam) * kza
@@ -416,18 +626,24 @@ def solve(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ver
                 gap = pobj - lag
                 if verbose:
                     print(f"{k:7d} res={res:.2e} p={pobj:.10g} L={lag:.10g} gap={gap:.2e} w={omega:.3g}")
+                rec = dict(status=None, k=k, iters=k, obj=lag, lag=lag, pobj=pobj, res=res, x=x, z=z, y=y, cert=cert,
+                           omega=omega, mvz=mvz, mvy=mvy)
                 if np.isfinite(lag) and res <= tol and gap <= tol * max(1.0, abs(lag)):
-                    return dict(status=0, obj=lag, pobj=pobj, iters=k, x=x, z=z, y=y)
+                    yield dict(rec, status=0)
+                    return
                 if k >= max_iters:
-                    return dict(status=1, obj=best, pobj=pobj, iters=k, x=x, z=z, y=y)
+                    yield dict(rec, status=1, obj=best)
+                    return
                 fpr = np.sqrt(omega * mvz + mvy / omega)
                 if last_fpr < 0:
                     last_fpr = fpr
-                restart = (fpr <= 0.2 * last_fpr or (fpr <= 0.8 * last_fpr and fpr > prev_fpr)
+                restart = (fpr <= 0.2 * last_fpr or (fpr <= rs_nec * last_fpr and fpr > prev_fpr)
                            or k_since >= 0.36 * k)
+                dz, dy = np.sqrt(dsz), np.sqrt(dsy)
+                yield dict(rec, fpr=fpr, last_fpr=last_fpr, prev_fpr=prev_fpr, k_since=k_since, restart=restart,
+                           dz=dz, dy=dy)
                 prev_fpr = fpr
                 if restart:
-                    dz, dy = np.sqrt(dsz), np.sqrt(dsy)
                     if dz > 1e-10 and dy > 1e-10:
                         omega = float(np.clip(np.exp(0.5 * np.log(dy / dz) + 0.5 * np.log(omega)), om_lo, om_hi))
                     elif m.dred and dy > 1e-10:      # (reduced step 2: primal static -> weight x10, scalar_pass)
@@ -440,3 +656,12 @@ def solve(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ver
                 else:
                     ks_base += ce
         block += 1
+
+
+def solve(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, verbose=False, inline_reflect=False):
+    """blocks() run to its end (certified, iteration limit, or presolve-infeasible).
+    Returns dict(status, obj, pobj, iters, x, z, y)."""
+    for rec in blocks(m, lbi, ubi, tol=tol, max_iters=max_iters, check_every=check_every, verbose=verbose,
+                      inline_reflect=inline_reflect):
+        if rec["status"] is not None:
+            return {k: rec[k] for k in ("status", "obj", "pobj", "iters", "x", "z", "y") if k in rec}

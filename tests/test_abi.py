@@ -181,6 +181,104 @@ def test_inline_reflection_equals_tracked_activity(name, k):
         assert abs(a["iters"] - b["iters"]) <= 0.1 * a["iters"] + 16
 
 
+@pytest.mark.parametrize("name,k", CASES[:6])
+def test_stepped_mirror_equals_solve(name, k):
+    """ref_pdhg.blocks (one record per certificate iteration) run to its end is ref_pdhg.solve, value for value;
+    its records count k = 1, 1 + ce, ... and only the last carries a status."""
+    from ref_pdhg import RefModel, blocks, solve
+    data, variant, step, kw = build_args(name, k)
+    run = dict(tol=1e-6, max_iters=200, check_every=16)
+    a = solve(RefModel(data, variant, step=step, **kw), **run)
+    recs = list(blocks(RefModel(data, variant, step=step, **kw), **run))
+    b = recs[-1]
+    assert [r["k"] for r in recs] == [1 + 16 * i for i in range(len(recs))]
+    assert all(r["status"] is None for r in recs[:-1]) and b["status"] == a["status"]
+    assert (a["iters"], a["obj"], a["pobj"]) == (b["iters"], b["obj"], b["pobj"])
+    for q in ("x", "z", "y"):
+        assert np.array_equal(a[q], b[q]), q
+
+
+def test_sorted_projection_equals_row_loop():
+    """proj_simplex_rows_sorted (every row at once) gives proj_simplex_rows' values bit for bit, masked rows,
+    empty rows and ties included."""
+    from ref_pdhg import proj_simplex_rows, proj_simplex_rows_sorted
+    rng = np.random.default_rng(0)
+    for t in range(100):
+        R, N = int(rng.integers(1, 9)), int(rng.integers(1, 40))
+        V = np.round(rng.standard_normal((R, N)) * rng.choice([1e-3, 1, 50]), int(rng.integers(0, 4)))
+        mask = rng.random((R, N)) < rng.choice([0.1, 0.5, 1.0])
+        a, b = proj_simplex_rows(V, mask), proj_simplex_rows_sorted(V, mask)
+        assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), t
+
+
+def test_mirror_engine_certificate_equals_plain_one_at_a_feasible_point():
+    """ref_pdhg.engine_certificate (what the kernels' certificate pass reports: repaired point, better of the plain
+    and the repaired bound) on an LP the mirror solves to 1e-9: the repaired objective and bound bracket the LP
+    value as the plain ones do, the repair moves nothing that matters, and no column is short of its c."""
+    from ref_pdhg import RefModel, blocks
+    from gpu_cases import G
+    for name, k in (("syn_4x3_s0_r0.5_NeptuneMinDelayAndUtilization", 0), ("syn_4x3_s0_r0.5_NeptuneMinDelayAndUtilization", 2)):
+        data, variant, step, kw = build_args(name, k)
+        recs = list(blocks(RefModel(data, variant, step=step, **kw), tol=1e-8, max_iters=20000, check_every=16,
+                           engine=True))
+        r = recs[-1]
+        assert r["status"] == 0, (name, k)
+        c = r["cert"]
+        ref = G[name]["models"][k]["lp_objective"]
+        scale = max(1.0, abs(ref))
+        assert r["lag"] <= c["lagr"] <= ref + 1e-6 * scale, (name, k, r["lag"], c["lagr"], ref)
+        assert abs(c["pobj"] - ref) <= 1e-5 * scale and c["res"] <= 1e-5, (name, k, c["pobj"], ref, c["res"])
+
+
+def _build_refusal(N, relaxation=0):
+    from core.engine.lp import debug_build
+    from core.utils import data_to_solver_input
+    from core.utils.synthetic import synthetic_payload
+    data = data_to_solver_input(synthetic_payload(N, 2, seed=0, rho=0.002), with_db=False)
+    return debug_build(data, "MinDelayAndUtilization", relaxation=relaxation)
+
+
+def test_build_admits_the_widest_rows_the_certificate_pass_holds():
+    """nep_model_create / nep_debug_build admit exactly the widths whose certificate x pass fits its LDS cap at the
+    smallest tile (nep_internal.h x_lds_bytes / fac_lds_bytes, the launchers' own formula): the largest N builds,
+    the next N with a wider padded row is refused with the largest supported N in the message, and so is 2048."""
+    import iter_cases as ic
+    from core.engine.lp import EngineUnavailable, RELAX_FACILITY
+    nmax = ic.max_nodes()
+    # 104 bytes per padded destination at 4 waves against 144 KiB; the static scalar partials (4 x 36 doubles)
+    # leave the launch within the 160 KiB of a CU
+    assert nmax == 1416 and ic.x_lds_bytes(4, nmax, True) + 4 * 36 * 8 <= 160 * 1024
+    assert ic.x_lds_bytes(4, nmax + 4, True) > ic.LDS_CAP
+    got = _build_refusal(nmax)
+    assert got["n_int"] == 2 * nmax + nmax
+    for N in (nmax + 1, 2048):
+        with pytest.raises(EngineUnavailable, match=rf"largest supported n_nodes: {nmax}\b"):
+            _build_refusal(N)
+    fmax = 1472       # facility relaxation: 100 bytes per padded destination
+    assert _build_refusal(fmax, RELAX_FACILITY)["n_int"] == 3 * fmax
+    for N in (fmax + 1, 2048):
+        with pytest.raises(EngineUnavailable, match=rf"largest supported n_nodes: {fmax}\b"):
+            _build_refusal(N, RELAX_FACILITY)
+
+
+def test_iterate_matrix_reaches_every_dispatchable_variant():
+    """The runs of test_gpu_iterates.py launch every x_pass<CPL, CHECK, INIT, FIRST, TW> the launchers can dispatch
+    (iter_cases.tile_waves is nep_kernels.hip tile_waves): all of CPL 1 / 2 / 4 / 8 x TW 4 / 8 / 16 x INIT / CHECK /
+    FIRST / STEADY except CPL 8 at TW 16 (capped to 8 waves) and the certificate passes whose LDS passes the cap
+    (CPL 4 at TW 16, CPL 8 at TW 8 and 16), which no admitted width and slot count reaches."""
+    import iter_cases as ic
+    ran = set()
+    for N, step, ns, box in ic.matrix():
+        ran |= ic.variants(N, ns)
+    can = ic.dispatchable()
+    every = {(c, t, kd) for c in (1, 2, 4, 8) for t in (4, 8, 16) for kd in ic.KINDS}
+    assert every - can == {(8, 16, kd) for kd in ic.KINDS} | {(4, 16, "CHECK"), (8, 8, "CHECK")}
+    assert ran == can, sorted(can - ran)
+    # the full-width shapes run the production tile only, the extra-chunk ones all three
+    assert all(ic.tile_waves(N, 256, chk) == 4 for N in ic.full_width() for chk in (False, True))
+    assert {ic.tile_waves(N, ns, False) for N in ic.EXTRA_CHUNK[:3] for ns in ic.SLOT_COUNTS} == {4, 8, 16}
+
+
 def test_facility_relaxation_build():
     """nep_debug_build of the B&B's facility relaxation (NEP_RELAX_FACILITY, API 7): its dual rows are C3, C5
     and c[f,j] <= n[j] (2N + FN; the x <= c rows are per routing entry, outside the dual vector), the integer

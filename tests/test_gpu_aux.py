@@ -94,6 +94,65 @@ def test_flows_entries_and_checks(name, k):
         m.close()
 
 
+@pytest.mark.parametrize("N", (258, 1026))
+def test_wide_rows_flows_entries_and_checks(N):
+    """The same read-outs on rows of two (N = 258) and eight (N = 1026) 16-byte chunks per lane, one chunk past a
+    lane boundary plus two padding columns: the root and the leaf-type box of tests/iter_cases.py stopped at their
+    certificate iteration 65 (no convergence needed: any routing state serves).  References from the aggregated
+    rows (nep_lp_get_rows) in fp64: a pooled row stands for its m zero-workload sources."""
+    import iter_cases as ic
+    from core.engine.lp import LPModel, LP_ITERATION_LIMIT
+    data = ic.instance(N)
+    F = ic.F
+    m = LPModel(data, ic.VARIANT, step=1, alpha=ic.ALPHA, max_batch=2)
+    try:
+        lb, ub = ic.boxes(N, m.n_int)
+        r = m.solve([0, 1], lb, ub, tol=1e-12, max_iters=65, check_every=16)
+        assert (r["status"] == LP_ITERATION_LIMIT).all() and (r["iters"] == 65).all(), r
+        W = np.asarray(data.workload_matrix, float)
+        D = np.asarray(data.node_delay_matrix, float)
+        cpr = np.asarray(data.core_per_req_matrix, float)
+        for slot in (0, 1):
+            xb, rf, rs = m.rows(slot)
+            x = xb.astype(np.float64)
+            z, _ = m.solution(slot, dense_x=False)
+            mult = np.where(rs >= 0, 1.0, (W[rf] == 0).sum(axis=1))          # sources a row stands for
+            wrow = np.where(rs >= 0, W[rf, np.maximum(rs, 0)], 0.0)
+            onehot = (rf[None, :] == np.arange(F)[:, None]).astype(float)     # [F, R]
+            flow = onehot @ (mult[:, None] * x)
+            wflow = onehot @ ((rs >= 0)[:, None] * x)
+            # flows: fp64 sums on the device, stored as float32 (one rounding; sums in another order)
+            fl = m.flows([slot])[0]
+            fl2, wfl = m.flows([slot], split=True)
+            assert np.array_equal(fl2[0], fl)
+            assert np.all(np.abs(fl - flow) <= 2.0 ** -23 * np.abs(flow) + 1e-12)
+            assert np.all(np.abs(wfl[0] - wflow) <= 2.0 ** -23 * np.abs(wflow) + 1e-12)
+            # routing entries: x > 0.001, np.round(x, 3), per aggregated row
+            row, dst, val = m.routing_entries(slot)
+            rr, jj = np.nonzero(x > 0.001)
+            got = dict(zip(zip(row.tolist(), dst.tolist()), val.tolist()))
+            want = {(int(a), int(b)): float(np.round(x[a, b], 3)) for a, b in zip(rr, jj)}
+            assert len(got) == len(row) and got == want
+            assert (jj >> 8).max() == (N - 1) >> 8           # (entries in the last chunk index)
+            # scorers / checkers
+            sc = m.score_check(slot)
+            loaded = rs >= 0
+            delay = float((wrow[loaded, None] * D[rs[loaded]] * x[loaded]).sum())
+            assert abs(sc["network_delay"] - delay) <= 1e-10 * max(1.0, abs(delay))
+            cm = z[:F * N].reshape(F, N)
+            cb = cm != 0
+            assert sc["bad_c_x"] == int(((flow > np.where(cb, 1e6, 0.0)) | (flow + 1e-6 < np.where(cb, 1.0, 0.0))).sum())
+            cpu = (cpr * (onehot @ (wrow[:, None] * x))).sum(axis=0)
+            assert sc["bad_cpu"] == int((cpu > np.asarray(data.node_cores_matrix, float) + 1e-6).sum())
+            mem = (np.asarray(data.function_memory_matrix, float)[:, None] * cb).sum(axis=0)
+            assert sc["bad_memory"] == int((mem > np.asarray(data.node_memory_matrix, float)).sum())
+            dev = np.abs(x.sum(axis=1) - 1.0)
+            assert sc["bad_handle"] == int((mult * ~(dev < 0.1)).sum())
+            assert sc["nodes_used"] == int((z[F * N:F * N + N] != 0).sum())
+    finally:
+        m.close()
+
+
 @pytest.mark.parametrize("name,k", CASES[:2])
 def test_batched_solutions_equal_single_reads(name, k):
     """nep_lp_get_solutions (API 8, the B&B's one read per advance) returns, slot for slot, what

@@ -94,6 +94,54 @@ def test_submit_ex_per_lp_budgets_match_separate_submits():
         assert abs(per[s][2] - ref) <= TOL * max(1.0, abs(ref))
 
 
+def test_submit_ex_of_fully_fixed_boxes_fills_the_staging():
+    """nep_lp_submit_ex stages two doubles per bound change and, behind them, two per LP (budget, bound stop).  With
+    max_batch boxes that change every integer variable of a model without base-fixed variables (rounding leaves:
+    every c and n fixed) that is 2 B n_int + 2 B doubles, the most a submit can stage: the results must equal those
+    of separate submits with the same budgets."""
+    import iter_cases as ic
+    from core.engine.lp import LPModel, LP_ITERATION_LIMIT, debug_presolve
+    N, B = 26, 4
+    data = ic.instance(N)
+    n_int = ic.F * N + N
+    lb = np.zeros((B, n_int))
+    for b in range(B):                              # B different leaves: function f on its b-th .. open destinations
+        for f in range(ic.F):
+            for j in ic.leaf_open(N, f)[b:]:
+                lb[b, f * N + j] = 1.0
+                lb[b, ic.F * N + j] = 1.0
+    ub = lb.copy()
+    free = np.stack([np.full(n_int, -np.inf), np.full(n_int, np.inf)])
+    ok, _, box, _ = debug_presolve(data, ic.VARIANT, np.vstack([free[:1], lb]), np.vstack([free[1:], ub]),
+                                   step=1, alpha=ic.ALPHA)
+    assert ok.all()
+    for b in range(B):                              # every variable's bounds differ from the base box
+        assert ((box[b + 1, 0] != box[0, 0]) | (box[b + 1, 1] != box[0, 1])).all()
+    budgets = np.array([17, 33, 49, 65], np.int64)
+
+    def run(per):
+        m = LPModel(data, ic.VARIANT, step=1, alpha=ic.ALPHA, max_batch=B)
+        kw = dict(tol=1e-12, check_every=16)
+        if per:
+            st = m.submit(np.arange(B), lb, ub, max_iters=budgets, bound_res=np.zeros(B), **kw)
+        else:
+            st = np.concatenate([m.submit([s], lb[s:s + 1], ub[s:s + 1], max_iters=int(budgets[s]), **kw)
+                                 for s in range(B)])
+        assert (st == LP_ITERATION_LIMIT).all()
+        got = {}
+        while m.active():
+            r = m.advance(1)
+            for i, s in enumerate(r["slots"]):
+                got[int(s)] = (int(r["status"][i]), int(r["iters"][i]), float(r["obj"][i]), float(r["primal_obj"][i]))
+        m.close()
+        return got
+
+    per, sep = run(True), run(False)
+    assert sorted(per) == list(range(B))
+    for s in range(B):
+        assert per[s] == sep[s], (s, per[s], sep[s])
+        assert per[s][:2] == (LP_ITERATION_LIMIT, budgets[s])
+
 
 def test_copy_states_equals_copies_in_order():
     """API 12 nep_lp_copy_states: a chain of warm-start copies in one call (a destination read by a later pair, a
