@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define NEP_API_VERSION 12
+#define NEP_API_VERSION 13
 
 /* variants: neptune.py:41-66 (NeptuneMinDelay / MinUtilization / MinDelayAndUtilization) */
 enum { NEP_MIN_DELAY = 0, NEP_MIN_UTILIZATION = 1, NEP_MIN_DELAY_AND_UTILIZATION = 2 };
@@ -178,6 +178,26 @@ int nep_lp_get_solution(void *model, int32_t slot, double *z_int, float *x_dense
 int nep_lp_get_solutions(void *model, int32_t n, const int32_t *slots, double *z_out);
 /* API 12: nep_lp_get_flows and nep_lp_get_solutions of the same n slots in one device round trip (one wait) */
 int nep_lp_get_flows_solutions(void *model, int32_t n, const int32_t *slots, float *flows, double *z_out);
+/* API 13, NEP_RELAX_FACILITY models: the reduced costs of z_int (c, then n) that the slot's bound was computed
+ * with, in the objective's units, and that bound: for every k and every t in [lb_k, ub_k], each point of the
+ * node's box with z_k = t has LP objective >= bound[b] + rc[b][k] * t - min(rc[b][k] * lb_k, rc[b][k] * ub_k).
+ * (The box is the node's as the engine holds it after presolve: nep_debug_state's lb / ub.)  bound[b] is the
+ * Lagrangian value those reduced costs priced — the best one among the slot's certificate checks — and never
+ * exceeds the obj nep_lp_advance reported for that LP.  NEP_ERR_STATE for an iterating slot and for a slot that
+ * has kept none: no certificate check yet, an LP presolve refused, or an LP whose box fixes every variable that
+ * carries cost (its value is the fixed point's objective, not a Lagrangian).  NEP_ERR_ARG for a reference-relaxation
+ * model (its bound uses repaired big-M prices and, in step 2, the exact disruption block, where a c has a
+ * piecewise-linear cost, not a reduced cost), a bad slot, or a NULL output.  nep_lp_copy_state(s) copies them with
+ * the rest of a slot's state (the node box is not part of that state: it is the destination's own). */
+int nep_lp_get_reduced_costs(void *model, int32_t n, const int32_t *slots, double *rc /* [n][n_int] */,
+                             double *bound /* [n] */);
+/* the variables that inequality closes at `cutoff`: k with lb_k < ub_k, rc_k != 0 and bound + |rc_k| (ub_k - lb_k) >
+ * cutoff (fp64, the product rounded before the sum), in ascending k, with the value to fix z_k at (lb_k if rc_k > 0,
+ * else ub_k): for a binary z_k, every point of the box with z_k at its other value costs more than cutoff.  The box
+ * is the slot's own (the LP it solved).  Count-only when capacity is too small, as nep_lp_routing_entries.  Compacted
+ * on the device: one small read per call. */
+int nep_lp_rc_fixings(void *model, int32_t slot, double cutoff, int64_t capacity, int64_t *n_fix,
+                      int32_t *idx, double *val);
 /* aggregated routing rows (host float, R*N) and the row map (row_f, row_src; src = -1: pooled
  * zero-workload sources of function f, each routed identically). */
 int nep_lp_get_rows(void *model, int32_t slot, float *xbar, int32_t *row_f, int32_t *row_src);
@@ -306,7 +326,8 @@ typedef struct {
   int32_t branching;               /* API 12: 0 n by inflow, then c by flow; 1 pseudo-cost (product score);
                                       2 reliability branching: pseudo-costs, strong-branching probes while unreliable */
   int32_t strong_cands, strong_rel;  /* branching 2: candidates scored, observations per direction to be reliable */
-  int32_t reserved_p;
+  int32_t rc_fixing;               /* API 13: 1 = reduced-cost fixing at the bound model's branching nodes (needs the
+                                      engine's rc_fixings call and an incumbent); 0 (default): off */
   int64_t strong_iters;            /* branching 2: iteration budget of a probe LP */
   double objective_unit;           /* with objective_integral: the objective's integral unit (<= 0: 1) — e.g. alpha / N
                                       for MinDelayAndUtilization without workload, whose objective is alpha / N sum n */
@@ -329,6 +350,9 @@ typedef struct {
   int64_t rebalanced, sync_calls;  /* sharded: open nodes imported from other ranks; collectives answered */
   double agreed_incumbent;         /* min(this rank's incumbent, the ranks' agreed one) */
   int64_t strong_nodes, strong_lps, strong_iterations, strong_decided;   /* branching 2: nodes that probed, probes */
+  int64_t rc_fixed, rc_calls;      /* API 13, rc_fixing: variables fixed by reduced cost, rc_fixings calls made */
+  int64_t rc_children_pruned, rc_leaves_dropped;   /* children whose branching value / rounding leaves whose
+                                                      placement a fixing contradicts (no LP) */
 } nep_bnb_stats;
 
 #define NEP_BNB_DONE 0   /* the search ended (no open node, or a stop): stats / incumbent are final */
@@ -363,6 +387,9 @@ typedef struct {
   int (*copy_states)(void *ctx, int32_t n, const int32_t *src_slots, const int32_t *dst_slots);
   /* optional (NULL: get_flows, then get_solutions): nep_lp_get_flows_solutions' contract */
   int (*get_flows_solutions)(void *ctx, int32_t n, const int32_t *slots, float *flows, double *z_out);
+  /* API 13, optional (NULL: the tree never fixes by reduced cost): nep_lp_rc_fixings' contract */
+  int (*rc_fixings)(void *ctx, int32_t slot, double cutoff, int64_t capacity, int64_t *n_fix, int32_t *idx,
+                    double *val);
 } nep_bnb_engine;
 
 /* NULL on a bad argument (nep_last_error says which): batch < 1, a layout outside n_int, no working slot left

@@ -46,6 +46,7 @@ import itertools
 import math
 import os
 import time
+import warnings
 from collections import deque
 
 import numpy as np
@@ -100,12 +101,13 @@ class BnBResult:
         self.inflight_sum = 0           # LPs in flight summed over the advance calls (mean: / advance_calls)
         self.native = False             # the search ran on the native tree (csrc/nep_bnb.cpp)
         self.strong = None              # (native, branching 2) strong-branching probe counts
+        self.rc = None                  # (native) reduced-cost fixing: variables fixed, calls, children / leaves cut
 
     def as_dict(self):
         d = {k: getattr(self, k) for k in ("status", "objective", "bound", "nodes", "leaves", "lps", "certified",
                                            "lp_iterations", "unresolved", "seconds", "polished", "repaired",
                                            "lp_status", "lp_status_kind", "drained", "timing",
-                                           "heuristic_incumbents", "routing_warm", "native", "strong")}
+                                           "heuristic_incumbents", "routing_warm", "native", "strong", "rc")}
         d["inflight_mean"] = self.inflight_sum / max(1, self.advance_calls)
         d["resolved"] = sum(v for k, v in self.lp_status.items() if k not in ("limit", "numerical"))
         it = np.asarray(self.lp_iters, np.float64)
@@ -159,7 +161,8 @@ class BranchAndBound:
                  retry_res=math.inf, unit_flow_leaves=True, node_max_iters=None, bound_lp=None, bound_gap=1e-4,
                  trace=None, rebalance_every=8, primal=None, primal_every=0,
                  leaf_routing_warm=False, root_check_every=64, objective_integral=False, warm_weight_ref=0.0,
-                 native=None, step2_native=None, branching=0, strong_cands=8, strong_rel=2, strong_iters=256):
+                 native=None, step2_native=None, branching=0, strong_cands=8, strong_rel=2, strong_iters=256,
+                 rc_fixing=False):
         self.lp = lp
         self.two = bound_lp is not None
         self.N, self.F = lp.N, lp.F
@@ -228,6 +231,11 @@ class BranchAndBound:
         # strong_cands best candidates) while a candidate's pseudo-costs rest on fewer than strong_rel observations
         self.branching = int(branching)
         self.strong_cands, self.strong_rel, self.strong_iters = int(strong_cands), int(strong_rel), int(strong_iters)
+        # reduced-cost fixing (native tree, facility bound model; DESIGN.md §7 "Reduced-cost fixing"): once an incumbent
+        # is known, a branching node about to branch fixes, in both children, every free c / n whose reduced cost
+        # shows that moving it costs more than the pruning cutoff (nep_lp_rc_fixings).  Off by default.
+        self.rc_fixing = bool(rc_fixing)
+        self._rc_warned = False
         # (the leaf / reference model only — the model whose node LPs the replay measured; the facility relaxation
         # keeps the parent-relative band: 256x128 / 20 s gap 0.51 % with it, 0.82 % with the band on both)
         for m_ in (lp,):
@@ -839,7 +847,7 @@ class BranchAndBound:
                       node_limit=int(min(float(self.node_limit), 2.0 ** 62)), time_limit=float(self.time_limit or 0.0),
                       world=int(comm.world), rank=int(comm.rank), branching=self.branching,
                       strong_cands=self.strong_cands, strong_rel=self.strong_rel, strong_iters=self.strong_iters,
-                      objective_unit=float(self.objective_unit))
+                      rc_fixing=1 if self.rc_fixing else 0, objective_unit=float(self.objective_unit))
         py_engines = []
         if hasattr(lp, "_h"):
             tree = lib.nep_bnb_create(lp._h, self.bound_lp._h if self.two else None, ctypes.byref(p),
@@ -960,6 +968,7 @@ class BranchAndBound:
         res.rebalanced = int(st.rebalanced)
         res.strong = {k: int(getattr(st, k)) for k in ("strong_nodes", "strong_lps", "strong_iterations",
                                                        "strong_decided")}
+        res.rc = {k: int(getattr(st, k)) for k in ("rc_fixed", "rc_calls", "rc_children_pruned", "rc_leaves_dropped")}
         res.split_hash = int(st.split_hash) if split_seen else None
         t_end = time.perf_counter()
         res.bound = float(st.bound)
@@ -994,6 +1003,9 @@ class BranchAndBound:
     def solve(self):
         if self._native_ok(self.comm):
             return self._solve_native()
+        if self.rc_fixing and not self._rc_warned:
+            self._rc_warned = True
+            warnings.warn("rc_fixing is a feature of the native tree search: this module's loop ignores it")
         t0 = self.t0 = time.time()
         self.res = res = BnBResult()
         lp = self.lp

@@ -18,7 +18,7 @@ STEP1, STEP2_DELETE, STEP2_CREATE = 1, 2, 3
 LP_OPTIMAL, LP_ITERATION_LIMIT, LP_INFEASIBLE, LP_CUTOFF, LP_NUMERICAL, LP_BOUND = 0, 1, 2, 3, 4, 5
 VARIANTS = {"MinDelay": MIN_DELAY, "MinUtilization": MIN_UTILIZATION,
             "MinDelayAndUtilization": MIN_DELAY_AND_UTILIZATION}
-API_VERSION = 12
+API_VERSION = 13
 RELAX_REFERENCE, RELAX_FACILITY = 0, 1
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -71,7 +71,7 @@ class BnbParams(ctypes.Structure):
                 ("retry_res", ctypes.c_double), ("flow_tol", ctypes.c_double), ("upper_bound", ctypes.c_double),
                 ("node_limit", ctypes.c_int64), ("time_limit", ctypes.c_double),
                 ("world", ctypes.c_int32), ("rank", ctypes.c_int32), ("branching", ctypes.c_int32),
-                ("strong_cands", ctypes.c_int32), ("strong_rel", ctypes.c_int32), ("reserved_p", ctypes.c_int32),
+                ("strong_cands", ctypes.c_int32), ("strong_rel", ctypes.c_int32), ("rc_fixing", ctypes.c_int32),
                 ("strong_iters", ctypes.c_int64), ("objective_unit", ctypes.c_double)]
 
 
@@ -89,7 +89,8 @@ class BnbStats(ctypes.Structure):
                [(k, ctypes.c_int64) for k in ("presplit_nodes", "presplit_lps", "presplit_certified", "rebalanced",
                                               "sync_calls")] + \
                [("agreed_incumbent", ctypes.c_double)] + \
-               [(k, ctypes.c_int64) for k in ("strong_nodes", "strong_lps", "strong_iterations", "strong_decided")]
+               [(k, ctypes.c_int64) for k in ("strong_nodes", "strong_lps", "strong_iterations", "strong_decided",
+                                              "rc_fixed", "rc_calls", "rc_children_pruned", "rc_leaves_dropped")]
 
 
 # nep_bnb_engine (API 12): the calls the native tree makes on one model
@@ -109,6 +110,8 @@ BNB_COPIES = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, _i3
 BNB_FLOWS_SOLS = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, _i32p, _fltp, _dblp)
 BNB_SUBMIT_EX = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, _i32p, _dblp, _dblp,
                                  ctypes.POINTER(LpOpts), _i64p, _dblp, _i32p)
+BNB_RC_FIX = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int64, _i64p,
+                              _i32p, _dblp)
 
 
 class BnbEngine(ctypes.Structure):
@@ -116,7 +119,7 @@ class BnbEngine(ctypes.Structure):
                 ("submit", BNB_SUBMIT), ("advance", BNB_ADVANCE), ("active", BNB_ACTIVE), ("copy_state", BNB_COPY),
                 ("set_params", BNB_PARAMS), ("get_flows", BNB_FLOWS), ("get_solutions", BNB_SOLS),
                 ("get_diag", BNB_DIAG), ("submit_ex", BNB_SUBMIT_EX), ("copy_states", BNB_COPIES),
-                ("get_flows_solutions", BNB_FLOWS_SOLS)]
+                ("get_flows_solutions", BNB_FLOWS_SOLS), ("rc_fixings", BNB_RC_FIX)]
 
 
 class PyBnbEngine:
@@ -124,15 +127,17 @@ class PyBnbEngine:
     active / copy_state / set_params / flows / solutions / diag, n_int, max_batch): lets the native tree search
     (csrc/nep_bnb.cpp, nep_bnb_create_engines) drive node LPs that are not the engine's — the CPU suite runs it
     over HiGHS (tests/oracle_lp.py).  A Python exception inside a call ends the search with NEP_ERR_STATE and is
-    kept in `error` (BranchAndBound re-raises it)."""
+    kept in `error` (BranchAndBound re-raises it).  A model with an rc_fixings(slot, cutoff) -> (idx, val) method
+    (LPModel.rc_fixings' contract) gives the tree its optional rc_fixings call, unless rc_fixings=False."""
 
-    def __init__(self, model, F, N, per_lp=True):
+    def __init__(self, model, F, N, per_lp=True, rc_fixings=True):
         self.model, self.F, self.N = model, int(F), int(N)
         self.n_int, self.max_batch = int(model.n_int), int(model.max_batch)
         self.error = None
         self.ex_calls = 0
         self.copies_calls = 0
         self.flows_sols_calls = 0
+        self.rc_calls = 0
         ni, mb = self.n_int, self.max_batch
         A = np.ctypeslib.as_array
 
@@ -210,6 +215,15 @@ class PyBnbEngine:
             o[:] = 0.0
             o[3] = float(d.get("pres", 0.0))
 
+        def rc_fix(_, slot, cutoff, capacity, n_fix, idx, val):
+            ki, kv = model.rc_fixings(int(slot), float(cutoff))
+            k = len(ki)
+            n_fix[0] = k
+            if k and capacity >= k:
+                A(idx, (k,))[:] = np.asarray(ki, np.int32)
+                A(val, (k,))[:] = np.asarray(kv, np.float64)
+            self.rc_calls += 1
+
         def active(_):
             try:
                 return int(model.active())
@@ -222,7 +236,9 @@ class PyBnbEngine:
                                BNB_FLOWS(guard(flows)), BNB_SOLS(guard(sols)), BNB_DIAG(guard(diag)),
                                BNB_SUBMIT_EX(guard(submit_ex)) if per_lp else BNB_SUBMIT_EX(),
                                BNB_COPIES(guard(copy_states)) if per_lp else BNB_COPIES(),
-                               BNB_FLOWS_SOLS(guard(flows_sols)) if per_lp else BNB_FLOWS_SOLS())
+                               BNB_FLOWS_SOLS(guard(flows_sols)) if per_lp else BNB_FLOWS_SOLS(),
+                               BNB_RC_FIX(guard(rc_fix)) if rc_fixings and hasattr(model, "rc_fixings")
+                               else BNB_RC_FIX())
 
 
 # every entry point declared in include/neptune_lp.h
@@ -237,7 +253,8 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_bnb_create", "nep_bnb_destroy", "nep_bnb_add_leaf", "nep_bnb_set_incumbent", "nep_bnb_event_data",
            "nep_bnb_run", "nep_bnb_get_stats", "nep_bnb_get_lp_iters", "nep_bnb_incumbent", "nep_bnb_set_step2",
            "nep_bnb_incumbent_event", "nep_bnb_debug_ibound", "nep_bnb_create_engines", "nep_bnb_sync_get",
-           "nep_bnb_sync_set", "nep_bnb_export_nodes", "nep_bnb_import_nodes")
+           "nep_bnb_sync_set", "nep_bnb_export_nodes", "nep_bnb_import_nodes", "nep_lp_get_reduced_costs",
+           "nep_lp_rc_fixings")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -283,6 +300,8 @@ def load_library(path=None):
     lib.nep_lp_get_flows_solutions.argtypes = [vp, i32, vp, vp, vp]
     lib.nep_lp_copy_routing.argtypes = [vp, i32, vp, i32]
     lib.nep_lp_get_solutions.argtypes = [vp, i32, pi32, _dp]
+    lib.nep_lp_get_reduced_costs.argtypes = [vp, i32, pi32, _dp, _dp]
+    lib.nep_lp_rc_fixings.argtypes = [vp, i32, ctypes.c_double, i64, pi64, pi32, _dp]
     lib.nep_round_leaves.argtypes = [i32, i32, _dp, _dp, ctypes.POINTER(ctypes.c_float), _dp, _dp, _dp, i32, pi32, _dp,
                                      _dp, _dp, pi32]
     lib.nep_get_stats.argtypes = [vp, ctypes.POINTER(Stats)]
@@ -609,6 +628,31 @@ class LPModel:
         _check(self._lib, self._lib.nep_lp_get_solutions(self._h, len(slots), _ptr(slots, ctypes.c_int32), _ptr(out)),
                "nep_lp_get_solutions")
         return out
+
+    def reduced_costs(self, slots):
+        """(rc [len(slots), n_int], bound [len(slots)]) of finished slots of a facility-relaxation model
+        (nep_lp_get_reduced_costs): the reduced costs of c, then n, each slot's bound was computed with — every point
+        of the node's box with z_k = t has LP objective >= bound + rc_k t - min(rc_k lb_k, rc_k ub_k)."""
+        slots = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        rc = np.zeros((len(slots), self.n_int))
+        bound = np.zeros(len(slots))
+        _check(self._lib, self._lib.nep_lp_get_reduced_costs(self._h, len(slots), _ptr(slots, ctypes.c_int32), _ptr(rc),
+                                                             _ptr(bound)), "nep_lp_get_reduced_costs")
+        return rc, bound
+
+    def rc_fixings(self, slot, cutoff):
+        """(idx, val): the variables of a finished slot that its reduced costs close at `cutoff`, ascending, and the
+        value each is fixed at (nep_lp_rc_fixings, compacted on the device)."""
+        n = ctypes.c_int64(0)
+        _check(self._lib, self._lib.nep_lp_rc_fixings(self._h, int(slot), float(cutoff), 0, ctypes.byref(n), None, None),
+               "nep_lp_rc_fixings")
+        k = n.value
+        idx = np.zeros(k, np.int32)
+        val = np.zeros(k)
+        if k:
+            _check(self._lib, self._lib.nep_lp_rc_fixings(self._h, int(slot), float(cutoff), k, ctypes.byref(n),
+                                                          _ptr(idx, ctypes.c_int32), _ptr(val)), "nep_lp_rc_fixings")
+        return idx, val
 
     def rows(self, slot):
         R = self.info.n_rows

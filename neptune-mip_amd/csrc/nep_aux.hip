@@ -322,6 +322,87 @@ hipError_t launch_gather_solutions(const DeviceView &v, const int32_t *slots, in
   return hipGetLastError();
 }
 
+// nep_lp_get_reduced_costs: per requested slot of a facility-relaxation model the reduced costs kept with its best
+// Lagrangian bound (buffer Ctrl::rc_best of rcbuf) and that bound, gathered like the solutions above: n slots, one
+// launch, one copy back.  bound = -inf: the slot has kept none (no certificate check yet); its row is then unspecified.
+__global__ void gather_reduced_costs(DeviceView v, const int32_t *__restrict__ slots, int ni, double *__restrict__ out,
+                                     double *__restrict__ bound) {
+  const int b = blockIdx.y;
+  const int s = slots[b];
+  const Ctrl *c = v.ctrl + s;
+  const double *r = v.rcbuf + (int64_t)s * v.srcbuf + (int64_t)(c->rc_best & 1) * ni;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < ni; k += gridDim.x * blockDim.x) out[(int64_t)b * ni + k] = r[k];
+  if (blockIdx.x == 0 && threadIdx.x == 0) bound[b] = c->rc_lagr;
+}
+
+hipError_t launch_gather_reduced_costs(const DeviceView &v, const int32_t *slots, int n, int ni, double *out,
+                                       double *bound, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int blocks = std::max(1, std::min(64, (ni + 255) / 256));
+  hipLaunchKernelGGL(gather_reduced_costs, dim3(blocks, n), dim3(256), 0, s, v, slots, ni, out, bound);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// reduced-cost fixing (nep_lp_rc_fixings): the variables k of one finished slot with lb_k < ub_k, rc_k != 0 and
+// rc_lagr + |rc_k| (ub_k - lb_k) > cutoff — every point of the node's box with z_k at the end its reduced cost
+// prices costs more than the cutoff — as a compacted (k, value to fix at) list in ascending k: count per wave of 64
+// variables (one ballot) -> compact_scan -> write (ballot prefix).  fp64 throughout; the sum is formed from the
+// rounded product (no fma), so a host filter of the dense read-out selects the same variables.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool rc_fixable(double rc, double lb, double ub, double lagr, double cutoff) {
+  return lb < ub && rc != 0.0 && __dadd_rn(lagr, __dmul_rn(fabs(rc), ub - lb)) > cutoff;
+}
+
+__global__ __launch_bounds__(256) void rc_fix_count(DeviceView v, int slot, double cutoff, int ni, int chunks,
+                                                    int32_t *__restrict__ cnt) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x * 4 + wave;
+  if (q >= chunks) return;
+  const Ctrl *c = v.ctrl + slot;
+  const double *rc = v.rcbuf + (int64_t)slot * v.srcbuf + (int64_t)(c->rc_best & 1) * ni;
+  const double *lb = v.lb + (int64_t)slot * v.sint, *ub = v.ub + (int64_t)slot * v.sint;
+  const int k = q * 64 + lane;
+  const bool keep = k < ni && rc_fixable(rc[k], lb[k], ub[k], c->rc_lagr, cutoff);
+  const uint64_t m = __ballot(keep);
+  if (lane == 0) cnt[q] = __popcll(m);
+}
+
+__global__ __launch_bounds__(256) void rc_fix_write(DeviceView v, int slot, double cutoff, int ni, int chunks,
+                                                    const int32_t *__restrict__ off, int32_t *__restrict__ out_idx,
+                                                    double *__restrict__ out_val) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x * 4 + wave;
+  if (q >= chunks) return;
+  const Ctrl *c = v.ctrl + slot;
+  const double *rc = v.rcbuf + (int64_t)slot * v.srcbuf + (int64_t)(c->rc_best & 1) * ni;
+  const double *lb = v.lb + (int64_t)slot * v.sint, *ub = v.ub + (int64_t)slot * v.sint;
+  const int k = q * 64 + lane;
+  double r = 0.0, l = 0.0, u = 0.0;
+  if (k < ni) { r = rc[k]; l = lb[k]; u = ub[k]; }
+  const bool keep = k < ni && rc_fixable(r, l, u, c->rc_lagr, cutoff);
+  const uint64_t m = __ballot(keep);
+  if (keep) {
+    const int pos = off[q] + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    out_idx[pos] = k;
+    out_val[pos] = r > 0.0 ? l : u;
+  }
+}
+
+// count_only: counts and their exclusive scan (off[chunks] = the total); else the write pass over the same scan
+hipError_t launch_rc_fixings(const DeviceView &v, int slot, double cutoff, int ni, int32_t *cnt, int32_t *off,
+                             int32_t *oidx, double *oval, bool count_only, hipStream_t s) {
+  const int chunks = (ni + 63) / 64;
+  const dim3 g((chunks + 3) / 4), b(256);
+  if (count_only) {
+    hipLaunchKernelGGL(rc_fix_count, g, b, 0, s, v, slot, cutoff, ni, chunks, cnt);
+    hipLaunchKernelGGL(compact_scan, dim3(1), dim3(1024), 0, s, cnt, chunks, off);
+  } else {
+    hipLaunchKernelGGL(rc_fix_write, g, b, 0, s, v, slot, cutoff, ni, chunks, off, oidx, oval);
+  }
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void copy_slots(SlotCopyN c) {
   const int k = blockIdx.y, q = blockIdx.z;
   if (k >= c.nseg || q >= c.npairs) return;

@@ -36,6 +36,7 @@
 
 namespace nep {
 int set_error(int code, const char *msg);   // nep_host.cpp: nep_last_error's thread-local message
+bool model_is_facility(void *model);        // nep_host.cpp: the handle is a NEP_RELAX_FACILITY model
 }
 
 namespace {
@@ -161,6 +162,9 @@ int op_params(void *c, double tol, double cut) { return nep_lp_set_params(c, tol
 int op_flows(void *c, int32_t n, const int32_t *sl, float *f) { return nep_lp_get_flows(c, n, sl, f); }
 int op_sols(void *c, int32_t n, const int32_t *sl, double *z) { return nep_lp_get_solutions(c, n, sl, z); }
 int op_diag(void *c, int32_t s, double *o) { return nep_lp_get_diag(c, s, o); }
+int op_rc_fix(void *c, int32_t s, double cut, int64_t cap, int64_t *n, int32_t *idx, double *val) {
+  return nep_lp_rc_fixings(c, s, cut, cap, n, idx, val);
+}
 
 int model_ops(void *lp, nep_bnb_engine *out) {
   nep_model_info info{};
@@ -181,6 +185,7 @@ int model_ops(void *lp, nep_bnb_engine *out) {
   out->submit_ex = op_submit_ex;
   out->copy_states = op_copies;
   out->get_flows_solutions = op_flows_sols;
+  out->rc_fixings = nep::model_is_facility(lp) ? op_rc_fix : nullptr;   // (a reference model keeps no reduced costs)
   return NEP_OK;
 }
 
@@ -294,7 +299,12 @@ struct NepBnb {
   int finish_block(Engine &eng, int nd);
   int finish_one(Engine &eng, int slot, const NodeP &node, int status, double o, double po, int64_t iters,
                  const float *flow, const double *z);
-  void round_all(const Node &node, const float *flow, const double *z, double bound, const Parent &me);
+  void round_all(const Node &node, const float *flow, const double *z, double bound, const Parent &me,
+                 const std::vector<int32_t> &fix_idx, const std::vector<double> &fix_val);
+  // reduced-cost fixing (p.rc_fixing): the fixings of a finished branching node at the pruning cutoff
+  int rc_fix(Engine &eng, int slot, const Node &node, std::vector<int32_t> &fix_idx, std::vector<double> &fix_val);
+  std::vector<int32_t> rcf_idx;   // (scratch of the engine call: n_int entries)
+  std::vector<double> rcf_val;
   int branch_var(const Node &node, const float *flow, const double *z) const;
   int branch_var_pc(const Node &node, const float *flow, const double *z) const;
   // pseudo-costs (p.branching == 1): per integer variable and direction, the sum / count of the bound gain per unit
@@ -802,7 +812,39 @@ static double step2_ibound(const nep_bnb_params &p, bool s2_create, double s2_ca
   return (2 * w + 1) * A - (O - kept);
 }
 
-void NepBnb::round_all(const Node &node, const float *flow, const double *z, double bound, const Parent &me) {
+// The variables of a finished branching node (slot) that its reduced costs close at the cutoff the tree prunes
+// with: a completion that moves one of them off the returned value has LP objective > incumbent - gap (the
+// Lagrangian is separable in c and n), i.e. it would be pruned.  Variables the node already fixes are left out.
+int NepBnb::rc_fix(Engine &eng, int slot, const Node &node, std::vector<int32_t> &fix_idx, std::vector<double> &fix_val) {
+  fix_idx.clear();
+  fix_val.clear();
+  if (!p.rc_fixing || !eng.ops.rc_fixings || !std::isfinite(incv())) return NEP_OK;
+  rcf_idx.resize(eng.n_int);
+  rcf_val.resize(eng.n_int);
+  int64_t nf = 0;
+  const int rc = eng.ops.rc_fixings(eng.ops.ctx, slot, incv() - gap_abs(incv()), eng.n_int, &nf, rcf_idx.data(),
+                                    rcf_val.data());
+  if (rc) return rc;
+  st.rc_calls += 1;
+  if (nf <= 0) return NEP_OK;
+  if (nf > eng.n_int) return bad(NEP_ERR_STATE, "rc_fixings returned more entries than variables");
+  std::vector<char> fixed(eng.n_int, 0);
+  for (int32_t i : node.idx)
+    if (i >= 0 && i < eng.n_int) fixed[i] = 1;
+  for (int64_t q = 0; q < nf; ++q) {
+    const int32_t k = rcf_idx[q];
+    const bool is_c = k >= p.c0 && k < p.c1, is_n = p.n0 >= 0 && k >= p.n0 && k < p.n1;
+    if (!(is_c || is_n) || fixed[k]) continue;   // (only the variables the tree branches on)
+    fixed[k] = 1;
+    fix_idx.push_back(k);
+    fix_val.push_back(rcf_val[q] > 0.5 ? 1.0 : 0.0);
+  }
+  st.rc_fixed += (int64_t)fix_idx.size();
+  return NEP_OK;
+}
+
+void NepBnb::round_all(const Node &node, const float *flow, const double *z, double bound, const Parent &me,
+                       const std::vector<int32_t> &fix_idx, const std::vector<double> &fix_val) {
   const int F = p.F, N = p.N, FN = F * N;
   std::vector<double> cfix(FN, -1.0), nfix;
   if (p.n0 >= 0) nfix.assign(N, -1.0);
@@ -835,6 +877,17 @@ void NepBnb::round_all(const Node &node, const float *flow, const double *z, dou
     leaf->val.reserve(leaf_idx.size());
     leaf->val.assign(cout.begin() + (size_t)q * FN, cout.begin() + (size_t)(q + 1) * FN);
     if (p.n0 >= 0) leaf->val.insert(leaf->val.end(), nout.begin() + (size_t)q * N, nout.begin() + (size_t)(q + 1) * N);
+    if (!fix_idx.empty()) {
+      // a leaf fixes every c and n, so the node's reduced-cost fixings add nothing to its box; one that places
+      // against a fixing costs more than the cutoff: dropped without an LP
+      bool against = false;
+      for (size_t t = 0; t < fix_idx.size() && !against; ++t) {
+        const int k = fix_idx[t];
+        const size_t at = (k >= p.c0 && k < p.c1) ? (size_t)(k - p.c0) : (size_t)FN + (size_t)(k - p.n0);   // (leaf_idx's order)
+        against = (leaf->val[at] > 0.5) != (fix_val[t] > 0.5);
+      }
+      if (against) { st.rc_leaves_dropped += 1; continue; }
+    }
     if (!seen.insert(key_of(leaf->val)).second) continue;
     leaf->bound = std::max(bound, ibound(leaf->idx, leaf->val));
     if (!pruned(leaf->bound)) pending.push_back(leaf);
@@ -956,9 +1009,15 @@ int NepBnb::finish_one(Engine &eng, int slot, const NodeP &node, int status, dou
   }
   st.nodes += 1;
   const Parent me{&eng, slot, eng.gen[slot]};
+  std::vector<int32_t> fix_idx;
+  std::vector<double> fix_val;
+  {
+    const int rc = rc_fix(eng, slot, *node, fix_idx, fix_val);
+    if (rc) return rc;
+  }
   {
     const double t0 = prof ? now_s() : 0.0;
-    round_all(*node, flow, z, bound, me);
+    round_all(*node, flow, z, bound, me, fix_idx, fix_val);
     if (prof) { pr_round += now_s() - t0; ++pr_rounds; }
   }
   if (p.primal_at_root && node->depth == 0 && !root_event_done) {
@@ -970,17 +1029,44 @@ int NepBnb::finish_one(Engine &eng, int slot, const NodeP &node, int status, dou
     ev_parent = me;
     ev_bound = bound;
   }
-  if (p.branching == 2 && start_strong(node, flow, z, bound, me)) {
+  // the node its children are made from: its own box and the reduced-cost fixings (the node itself when none)
+  NodeP base = node;
+  if (!fix_idx.empty()) {
+    base = std::make_shared<Node>(*node);
+    base->idx.insert(base->idx.end(), fix_idx.begin(), fix_idx.end());
+    base->val.insert(base->val.end(), fix_val.begin(), fix_val.end());
+  }
+  // (strong branching picks its candidates among the variables still free in `base`; its probes and children carry
+  // the fixings)
+  if (p.branching == 2 && start_strong(base, flow, z, bound, me)) {
     eng.free.push_back(slot);   // (its probes warm-start from this slot; they are submitted first)
     return NEP_OK;
   }
-  const int var = p.branching >= 1 ? branch_var_pc(*node, flow, z) : branch_var(*node, flow, z);
+  // the branching variable as without fixings (the node's own LP decides it).  One that a fixing decides has a child
+  // the fixing contradicts — pruned here, without an LP — and a child that is `base` itself, whose LP is this
+  // node's again: instead of re-solving it, `base` branches at once on the next variable of the rule.
+  auto choose = [&](const Node &from) {
+    return p.branching >= 1 ? branch_var_pc(from, flow, z) : branch_var(from, flow, z);
+  };
+  int var = choose(*node);
+  if (var >= 0 && std::find(fix_idx.begin(), fix_idx.end(), var) != fix_idx.end()) {
+    st.rc_children_pruned += 1;
+    var = choose(*base);
+    if (var < 0 && (int)base->idx.size() >= nb()) {   // the fixings decide every variable: `base` is a leaf
+      auto leaf = std::make_shared<Node>(*base);
+      leaf->bound = std::max(bound, ibound(leaf->idx, leaf->val));
+      leaf->kind = LEAF;
+      leaf->parent = me;
+      leaf->depth = node->depth + 1;
+      if (!pruned(leaf->bound)) push_heap(leaf);
+    }
+  }
   if (var >= 0) {
     for (double v : {1.0, 0.0}) {
       auto ch = std::make_shared<Node>();
-      ch->idx = node->idx;
+      ch->idx = base->idx;
       ch->idx.push_back(var);
-      ch->val = node->val;
+      ch->val = base->val;
       ch->val.push_back(v);
       ch->bound = std::max(bound, ibound(ch->idx, ch->val));
       ch->bvar = var;

@@ -84,11 +84,14 @@ void fac_x_pass(DeviceView v, const int32_t *__restrict__ slots, int plain, int 
   // stage 0: c[f, :].  Reduced cost cost - K^T y with C3 (mem_f y3), the x <= c rows of f (-sum_r lambda) and
   // the c <= n row (mu); every dual is the previous iteration's, so ĉ is known before the rows (PDHG's order)
   SmallAcc a0;
+  // certificate launches keep the reduced costs their Lagrangian is priced with (scalar_pass decides which buffer stays)
+  double *rcw = CHECK ? v.rcbuf + slot * v.srcbuf + (int64_t)ctrl->rc_cur * il.n_int : nullptr;
   for (int j = threadIdx.x; j < NP; j += kWave * TW) {
     if (j < N) {
       const int idx = f * N + j, k = il.oc + idx;
       const double rc = v.cost_int[k] - (v.mem_f[f] * y[dl.o3 + j] - (double)lsum[j] + y[dl.oQ + idx]);
       const double c_old = zi[k];
+      if (CHECK) rcw[k] = rc;
       const double ch = primal_step<CHECK>(v, zi, zia, lb, ub, k, rc, taud, restart, halp, lamd, a0);
       lCh[j] = ch;
       lRd[j] = 2.0 * ch - c_old;
@@ -523,8 +526,9 @@ __global__ __launch_bounds__(kNodeThreads) void fac_node_pass(DeviceView v, cons
     // each, C3 -Mem_j and C5 -cores_j, so its reduced cost is cost_n + sum_f mu[f, j] + Mem_j y3 + cores_j y5
     const double capM = v.capn[j], capC = v.capn[N + j];
     const double n_old = pn.z;
-    const double nn = primal_step_p<CHECK>(zi, zia, il.on + j, pn.cost + musum + capM * p3.y + capC * p5.y, pn, tau,
-                                           copy_anchor, halp, lam, a);
+    const double rcn = pn.cost + musum + capM * p3.y + capC * p5.y;
+    if (CHECK) v.rcbuf[slot * v.srcbuf + (int64_t)ctrl->rc_cur * il.n_int + il.on + j] = rcn;
+    const double nn = primal_step_p<CHECK>(zi, zia, il.on + j, rcn, pn, tau, copy_anchor, halp, lam, a);
     nref[lane] = 2.0 * nn - n_old;
     if (CHECK) {   // repaired n: the least value the repaired c (n >= c, Mem_j n >= its memory) and x̂ (cores_j
                    // n >= its CPU) allow, within the node box; C3 / C5 at that point

@@ -45,6 +45,10 @@ hipError_t launch_compact_f64(const double *vals, int rows, int cols, int64_t ld
                               hipStream_t s);
 hipError_t launch_copy_segments(const SlotCopy &c, hipStream_t s);
 hipError_t launch_copy_slots(const SlotCopyN &c, hipStream_t s);
+hipError_t launch_gather_reduced_costs(const DeviceView &v, const int32_t *slots, int n, int ni, double *out,
+                                       double *bound, hipStream_t s);
+hipError_t launch_rc_fixings(const DeviceView &v, int slot, double cutoff, int ni, int32_t *cnt, int32_t *off,
+                             int32_t *oidx, double *oval, bool count_only, hipStream_t s);
 hipError_t launch_gather_solutions(const DeviceView &v, const int32_t *slots, int n, int ni, double *out,
                                    hipStream_t s);
 hipError_t launch_power_iteration(const DeviceView &v, int iters, double *zx, double *zs, double *gx, double *gs,
@@ -204,6 +208,14 @@ struct Model {
   float *h_flows = nullptr;     // pinned staging of nep_lp_get_flows(_split): [2][max_batch][F*N] + slots
   double *h_sols = nullptr;     // pinned staging of nep_lp_get_solutions: [max_batch][n_int] + the slot list
   double *d_sols = nullptr;     // [max_batch][n_int]: the gathered solutions (gather_solutions)
+  // reduced costs of a facility model (nep_lp_get_reduced_costs / nep_lp_rc_fixings), allocated on first use
+  double *h_rc = nullptr;       // pinned staging: [max_batch][n_int + 1] (the bounds behind the rows) + the slot list
+  double *d_rc = nullptr;       // [max_batch][n_int + 1]: the gathered reduced costs, then the bounds
+  int32_t *d_rccnt = nullptr, *d_rcoff = nullptr;   // [ceil(n_int / 64) + 1]: fixings per wave of 64 variables, their scan
+  int32_t *d_rcidx = nullptr;   // [n_int] the compacted fixings
+  double *d_rcval = nullptr;
+  // per slot: the LP submitted last was refused by presolve, so the slot's kept reduced costs are an earlier LP's
+  std::vector<uint8_t> rc_stale;
   // pinned staging of nep_lp_submit's uploads (slots, change offsets / indices / bounds, exact flags): the
   // call returns without waiting for them; two stagings alternate, and a submit waits on the event of the
   // one it rewrites (recorded after that staging's copies, two submits earlier: normally long done)
@@ -220,6 +232,7 @@ struct Model {
     if (h_act) (void)hipHostFree(h_act);
     if (h_flows) (void)hipHostFree(h_flows);
     if (h_sols) (void)hipHostFree(h_sols);
+    if (h_rc) (void)hipHostFree(h_rc);
     for (int k = 0; k < 2; ++k) {
       if (h_sub_i[k]) (void)hipHostFree(h_sub_i[k]);
       if (h_sub_d[k]) (void)hipHostFree(h_sub_d[k]);
@@ -753,6 +766,7 @@ int build(Model &m, const nep_model_desc &d, bool host_power = true) {
 int setup_device(Model &m, int max_batch, void *stream) {
   m.max_batch = max_batch;
   m.busy.assign(max_batch, 0);
+  m.rc_stale.assign(max_batch, 0);
   if (stream) {
     m.stream = (hipStream_t)stream;
   } else {
@@ -867,6 +881,10 @@ int setup_dense(Model &m, const nep_model_desc &d) {
     for (int f = 0; f < F; ++f)
       for (int j = 0; j < N; ++j) rl[(size_t)f * NP + j] = (float)m.rhoL[(size_t)f * N + j];
     if ((rc = upload(m, &v.rho_l, rl))) return rc;
+    // the reduced costs the certificate launches keep (two buffers per slot; 2 MB per slot at 512x256)
+    v.srcbuf = 2 * (int64_t)m.il.n_int;
+    if ((rc = dalloc(m, &v.rcbuf, (size_t)B * v.srcbuf))) return rc;
+    HIPCHK(hipMemsetAsync(v.rcbuf, 0, sizeof(double) * B * v.srcbuf, m.stream));
     HIPCHK(hipMemsetAsync(v.lam, 0, sizeof(float) * B * v.sx, m.stream));
     HIPCHK(hipMemsetAsync(v.lsum, 0, sizeof(float) * B * v.slsum, m.stream));
   }
@@ -897,7 +915,13 @@ int setup_dense(Model &m, const nep_model_desc &d) {
   // (a submit stages at most one bound change per integer variable and LP — presolve_node appends an index once —
   // i.e. 2 x nchg <= 2 B n_int doubles, and nep_lp_submit_ex two more per LP behind them: its budgets / bound stops)
   if ((rc = dalloc(m, &m.d_sub_d, (size_t)2 * B * (v.sint + 1)))) return rc;
-  HIPCHK(hipMemsetAsync(v.ctrl, 0, sizeof(Ctrl) * B, m.stream));
+  {   // every slot's Ctrl zeroed, with no reduced costs kept (rc_lagr = -inf)
+    Ctrl c0;
+    std::memset(&c0, 0, sizeof(Ctrl));
+    c0.rc_lagr = -INF;
+    const std::vector<Ctrl> init((size_t)B, c0);
+    HIPCHK(hipMemcpy(v.ctrl, init.data(), sizeof(Ctrl) * B, hipMemcpyHostToDevice));
+  }
   HIPCHK(hipMemsetAsync(v.x, 0, sizeof(float) * B * v.sx, m.stream));
   HIPCHK(hipMemsetAsync(v.xa, 0, sizeof(float) * B * v.sx, m.stream));
   HIPCHK(hipMemsetAsync(v.acnt, 0, sizeof(int32_t) * B * m.R, m.stream));
@@ -1502,6 +1526,7 @@ int submit(Model &m, int n, const int32_t *slots, const double *lbi, const doubl
     const int s = slots[b];
     const NodeBox &nb = box[b];
     status[b] = nb.ok ? NEP_LP_ITERATION_LIMIT : NEP_LP_INFEASIBLE;
+    m.rc_stale[s] = nb.ok ? 0 : 1;
     if (!nb.ok) continue;
     m.busy[s] = 1;
     fresh.push_back(s);
@@ -1890,6 +1915,11 @@ int score_check(Model &m, int slot, double *out) {
 
 }  // namespace
 
+namespace nep {
+// (nep_bnb.cpp: nep_bnb_create gives the tree nep_lp_rc_fixings only for a facility-relaxation model)
+bool model_is_facility(void *model) { return model && static_cast<Model *>(model)->fac != 0; }
+}
+
 // =============================================================================================
 // C ABI
 // =============================================================================================
@@ -2088,6 +2118,92 @@ int nep_lp_get_flows_solutions(void *model, int32_t n, const int32_t *slots, flo
   return NEP_OK;
 }
 
+static const char *const kRcRefusal =
+    "reduced costs are kept by facility-relaxation models only (NEP_RELAX_FACILITY): the reference relaxation's bound "
+    "uses repaired big-M prices and, in step 2, the exact disruption block";
+
+// scratch of the reduced-cost calls, on first use
+static int ensure_rc(Model &m) {
+  const size_t ni = (size_t)m.il.n_int, B = (size_t)m.max_batch;
+  if (!m.h_rc) {
+    void *hp = nullptr;
+    if (hipHostMalloc(&hp, sizeof(double) * B * (ni + 2)) != hipSuccess)
+      return fail(NEP_ERR_NOMEM, "hipHostMalloc (reduced costs)");
+    m.h_rc = static_cast<double *>(hp);
+  }
+  int rc;
+  if (!m.d_rc && (rc = dalloc(m, &m.d_rc, B * (ni + 1)))) return rc;
+  if (!m.d_rccnt) {
+    const size_t chunks = (ni + 63) / 64;
+    if ((rc = dalloc(m, &m.d_rccnt, chunks + 1))) return rc;
+    if ((rc = dalloc(m, &m.d_rcoff, chunks + 1))) return rc;
+    if ((rc = dalloc(m, &m.d_rcidx, ni))) return rc;
+    if ((rc = dalloc(m, &m.d_rcval, ni))) return rc;
+  }
+  return NEP_OK;
+}
+
+int nep_lp_get_reduced_costs(void *model, int32_t n, const int32_t *slots, double *rc_out, double *bound_out) {
+  if (!model || (n > 0 && (!slots || !rc_out || !bound_out))) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (!m.fac) return fail(NEP_ERR_ARG, kRcRefusal);
+  if (n <= 0) return NEP_OK;
+  if (n > m.max_batch) return fail(NEP_ERR_ARG, "n > max_batch");
+  for (int b = 0; b < n; ++b) {
+    if (slots[b] < 0 || slots[b] >= m.max_batch) return fail(NEP_ERR_ARG, "slot out of range");
+    if (m.busy[slots[b]]) return fail(NEP_ERR_STATE, "slot is still iterating");
+    if (m.rc_stale[slots[b]]) return fail(NEP_ERR_STATE, "slot " + std::to_string(slots[b]) + " has no certificate check yet");
+  }
+  int rc = ensure_rc(m);
+  if (rc) return rc;
+  const size_t ni = (size_t)m.il.n_int;
+  // one gather and one copy back: the n rows, then the n bounds behind them
+  int32_t *hs = reinterpret_cast<int32_t *>(m.h_rc + (size_t)m.max_batch * (ni + 1));
+  std::memcpy(hs, slots, n * sizeof(int32_t));
+  double *d_bound = m.d_rc + (size_t)n * ni;
+  HIPCHK(hipMemcpyAsync(m.d_new, hs, n * sizeof(int32_t), hipMemcpyHostToDevice, m.aux));
+  HIPCHK(launch_gather_reduced_costs(m.v, m.d_new, n, (int)ni, m.d_rc, d_bound, m.aux));
+  HIPCHK(hipMemcpyAsync(m.h_rc, m.d_rc, (size_t)n * (ni + 1) * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+  HIPCHK(hipStreamSynchronize(m.aux));
+  const double *hb = m.h_rc + (size_t)n * ni;
+  for (int b = 0; b < n; ++b)
+    if (!(hb[b] > -INF)) return fail(NEP_ERR_STATE, "slot " + std::to_string(slots[b]) + " has no certificate check yet");
+  std::memcpy(rc_out, m.h_rc, sizeof(double) * n * ni);
+  std::memcpy(bound_out, hb, sizeof(double) * n);
+  return NEP_OK;
+}
+
+int nep_lp_rc_fixings(void *model, int32_t slot, double cutoff, int64_t capacity, int64_t *n_fix, int32_t *idx,
+                      double *val) {
+  if (!model || !n_fix) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (!m.fac) return fail(NEP_ERR_ARG, kRcRefusal);
+  if (slot < 0 || slot >= m.max_batch) return fail(NEP_ERR_ARG, "slot out of range");
+  if (m.busy[slot]) return fail(NEP_ERR_STATE, "slot is still iterating");
+  if (cutoff != cutoff) return fail(NEP_ERR_ARG, "cutoff is NaN");
+  const std::string none = "slot " + std::to_string(slot) + " has no certificate check yet";
+  if (m.rc_stale[slot]) return fail(NEP_ERR_STATE, none);
+  int rc = ensure_rc(m);
+  if (rc) return rc;
+  const int ni = m.il.n_int, chunks = (ni + 63) / 64;
+  HIPCHK(launch_rc_fixings(m.v, slot, cutoff, ni, m.d_rccnt, m.d_rcoff, nullptr, nullptr, true, m.aux));
+  // the total and the slot's kept bound in one wait
+  int32_t total = 0;
+  double lagr = -INF;
+  HIPCHK(hipMemcpyAsync(&total, m.d_rcoff + chunks, sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+  HIPCHK(hipMemcpyAsync(&lagr, &m.v.ctrl[slot].rc_lagr, sizeof(double), hipMemcpyDeviceToHost, m.aux));
+  HIPCHK(hipStreamSynchronize(m.aux));
+  if (!(lagr > -INF)) return fail(NEP_ERR_STATE, none);
+  *n_fix = total;
+  if (capacity < total || total == 0) return NEP_OK;   // size query (or nothing to write)
+  if (!idx || !val) return fail(NEP_ERR_ARG, "null argument");
+  HIPCHK(launch_rc_fixings(m.v, slot, cutoff, ni, m.d_rccnt, m.d_rcoff, m.d_rcidx, m.d_rcval, false, m.aux));
+  HIPCHK(hipMemcpyAsync(idx, m.d_rcidx, total * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+  HIPCHK(hipMemcpyAsync(val, m.d_rcval, total * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+  HIPCHK(hipStreamSynchronize(m.aux));
+  return NEP_OK;
+}
+
 int nep_lp_get_solution(void *model, int32_t slot, double *z_int, float *x_dense) {
   if (!model) return fail(NEP_ERR_ARG, "null model");
   Model &m = *static_cast<Model *>(model);
@@ -2167,7 +2283,10 @@ int nep_lp_copy_state(void *model, int32_t src, int32_t dst) {
   if (m.fac) {   // the x <= c duals and their per-(f, j) sums travel with the state
     seg(v.lam, v.sx);
     seg(v.lsum, v.slsum);
+    seg(v.rcbuf, v.srcbuf);   // the kept reduced costs travel with the Ctrl fields that name them (rc_best, rc_lagr)
   }
+  static_assert(SlotCopy::kMax >= 11, "a facility slot copies 11 segments");
+  m.rc_stale[dst] = m.rc_stale[src];
   HIPCHK(launch_copy_segments(c, m.aux));
   // no host wait: every later use of src / dst is ordered behind these copies — host reads and submits run
   // on `aux`, and a slot iterates on `stream` only after its submit's initialisation (ev_aux)
@@ -2203,7 +2322,9 @@ int nep_lp_copy_states(void *model, int32_t n, const int32_t *src, const int32_t
   if (m.fac) {
     seg(v.lam, v.sx);
     seg(v.lsum, v.slsum);
+    seg(v.rcbuf, v.srcbuf);
   }
+  static_assert(SlotCopyN::kSeg >= 11, "a facility slot copies 11 segments");
   // the same result as n nep_lp_copy_state calls in order: a launch takes pairs while none of them reads or writes
   // a slot an earlier pair of the launch writes, or writes a slot an earlier pair reads
   std::vector<int32_t> rd, wr;
@@ -2223,6 +2344,7 @@ int nep_lp_copy_states(void *model, int32_t n, const int32_t *src, const int32_t
     }
     c.src[c.npairs] = src[k];
     c.dst[c.npairs] = dst[k];
+    m.rc_stale[dst[k]] = m.rc_stale[src[k]];
     ++c.npairs;
     rd.push_back(src[k]);
     wr.push_back(dst[k]);

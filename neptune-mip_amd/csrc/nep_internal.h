@@ -176,6 +176,11 @@ struct Ctrl {
   int64_t polish_k0, polish_next;        // iteration polishing started; earliest iteration to start (-1: never)
   double bound_res;                      // > 0: stop with NEP_LP_BOUND once the bound converged (nep_lp_opts)
   int32_t infeas_hits, pad_;             // consecutive certificate checks whose Farkas test held
+  // facility relaxation, reduced costs (DeviceView::rcbuf; DESIGN.md §7 "Reduced-cost fixing"): the buffer the next
+  // certificate launch writes, the buffer kept with the best Lagrangian bound so far, and that bound — the Lagrangian
+  // the kept reduced costs were formed with (-inf: no check yet).  scalar_pass changes rc_best and rc_lagr together.
+  int32_t rc_cur, rc_best;
+  double rc_lagr;
 };
 
 // row-family offsets inside y / kz / rho / lo / hi
@@ -250,6 +255,11 @@ struct DeviceView {
   double rs_suff, rs_nec, rs_art, omega_smooth;
   int64_t max_iters;
   double bound_res;                      // submit option copied into each new slot's Ctrl (init_slot)
+  // facility relaxation: the reduced costs of c and n the certificate launches price the Lagrangian with, two
+  // buffers [2][n_int] per slot (Ctrl::rc_cur / rc_best); nullptr on a reference-relaxation model.  (Last, so the
+  // kernel-argument offsets of the fields above — and the plain passes' code — stay as they were.)
+  double *rcbuf;
+  int64_t srcbuf;
 };
 
 // device-to-device segments copied by one launch (nep_aux.hip copy_segments; byte counts multiples of 4)

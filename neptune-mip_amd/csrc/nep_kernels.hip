@@ -1439,6 +1439,18 @@ __global__ __launch_bounds__(256) void scalar_pass(DeviceView v, const int32_t *
     }
     if (lr > lagr) lagr = lr;
   }
+  // Facility relaxation: this launch's reduced costs of c and n (fac_x_pass / fac_node_pass wrote buffer rc_cur) stay
+  // when its Lagrangian is the best one they have been kept with; the next check then writes the other buffer, so
+  // the kept buffer always belongs to rc_lagr.  Decided here, ahead of every way this check can end (certified,
+  // bound stop, cutoff, limit); below, best_lagr takes the same lagr, so rc_lagr <= best_lagr <= the obj reported.
+  // An exact LP keeps none: its best_lagr is also raised to the repaired point's objective, which no reduced cost
+  // prices, and its box leaves nothing to fix.  Not while polishing: that launch's rc lacks the cost.  (lagr is the
+  // plain separable Lagrangian here: v.fac has no dual repair and no step 2.)
+  if (v.fac && !ctrl->polish && !ctrl->exact && lagr > ctrl->rc_lagr) {
+    ctrl->rc_lagr = lagr;
+    ctrl->rc_best = ctrl->rc_cur;
+    ctrl->rc_cur ^= 1;
+  }
   const double gap = pobj - lagr;
   const double tol = v.prm[0], cutoff = v.prm[1], gap_tol = v.prm[2];
   ctrl->pobj = pobj;
@@ -1643,6 +1655,8 @@ __global__ void init_slot(DeviceView v, const int32_t *__restrict__ slots, const
     ctrl->polish_k0 = 0;
     ctrl->polish_next = v.polish_after;   // this LP's submit option (-1: it never polishes)
     ctrl->best_lagr = -INFINITY;
+    ctrl->rc_lagr = -INFINITY;   // no reduced costs kept yet (a warm start does not inherit its parent's)
+    ctrl->rc_cur = ctrl->rc_best = 0;
     ctrl->pobj = ctrl->lagr = ctrl->pres = ctrl->gap = NAN;
   }
 }

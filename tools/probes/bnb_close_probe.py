@@ -6,7 +6,8 @@ run: status, incumbent, bound, relative gap, nodes, LPs, seconds — beside the 
 same instance's aggregated facility MIP on this container's CPU (the facility rows with C2's eps floor, exact for
 integral c / n; /tmp experiment, DESIGN.md §7 "Closing the search").
 
-  python3 tools/bnb_close_probe.py 48x24:60,64x32:120 [--rules 0,1] [--gap 1e-4] [--seed 0] [--out f.jsonl]
+  python3 tools/probes/bnb_close_probe.py 48x24:60,64x32:120 [--rules 0,1] [--gap 1e-4] [--seed 0] [--rc-fixing 1]
+                                          [--out f.jsonl]
 """
 import argparse
 import json
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--node-limit", type=float, default=1e9)
     ap.add_argument("--strong-iters", type=int, default=256)
     ap.add_argument("--strong-cands", type=int, default=8)
+    ap.add_argument("--rc-fixing", type=int, default=0, help="1: reduced-cost fixing at the branching nodes")
     ap.add_argument("--tag", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -53,7 +55,8 @@ def main():
             m = LPModel(data, "MinDelayAndUtilization", step=1, alpha=0.5, max_batch=a.batch + 2)
             bm = st1.bound_model(data, a.batch + 1)
             ov = dict(time_limit=float(secs or 60), root_max_iters=400000, gap=a.gap, branching=rule,
-                      node_limit=a.node_limit, strong_iters=a.strong_iters, strong_cands=a.strong_cands)
+                      node_limit=a.node_limit, strong_iters=a.strong_iters, strong_cands=a.strong_cands,
+                      rc_fixing=bool(a.rc_fixing))
             if a.node_iters:
                 ov["node_max_iters"] = a.node_iters
             if a.bound_gap:
@@ -68,6 +71,7 @@ def main():
             ref = HIGHS_OPT.get(size) if a.seed == 0 else None
             row = {"instance": size, "seed": a.seed, "rule": rule, "tag": a.tag, "node_iters": a.node_iters,
                    "bound_gap": a.bound_gap, "time_limit": float(secs or 60), "status": res.status, "strong": res.strong,
+                   "rc_fixing": a.rc_fixing, "rc": res.rc,
                    "incumbent": inc, "bound": res.bound,
                    "rel_gap": None if inc is None else (inc - res.bound) / max(1.0, abs(inc)),
                    "nodes": res.nodes, "lps": res.lps, "seconds": time.time() - t0, "native": res.native,
