@@ -273,6 +273,11 @@ int nep_debug_build(const nep_model_desc *desc, double *eta, double *rho, double
  * 1 = feasible; box_* [n][2][n_int] (may be NULL): the resulting node bounds (lb then ub). */
 int nep_debug_presolve(const nep_model_desc *desc, int32_t n, const double *lb_int, const double *ub_int,
                        int32_t *ok_full, int32_t *ok_node, double *box_full, double *box_node);
+/* host-only: how a block of `na` iterating slots of a model of n_nodes x n_functions (relaxation as in
+ * nep_model_desc) is launched.  out3 = {slots of the first slot group when the block runs as two groups
+ * (NEP_BLOCK_GROUPS=2), 0 when it runs as one; waves per x-pass workgroup of a launch over na slots, plain
+ * variant; the same, certificate variant}.  Lets the CPU test-suite check the split rule without a GPU. */
+int nep_debug_block_split(int32_t n_nodes, int32_t n_functions, int32_t relaxation, int32_t na, int32_t *out3);
 void nep_reset_stats(void *model);
 
 /* API 8: the routing state (x and its projection thresholds) of a finished slot of ANOTHER model of the same

@@ -254,7 +254,7 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_bnb_run", "nep_bnb_get_stats", "nep_bnb_get_lp_iters", "nep_bnb_incumbent", "nep_bnb_set_step2",
            "nep_bnb_incumbent_event", "nep_bnb_debug_ibound", "nep_bnb_create_engines", "nep_bnb_sync_get",
            "nep_bnb_sync_set", "nep_bnb_export_nodes", "nep_bnb_import_nodes", "nep_lp_get_reduced_costs",
-           "nep_lp_rc_fixings")
+           "nep_lp_rc_fixings", "nep_debug_block_split")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -348,6 +348,8 @@ def load_library(path=None):
     # pointer casts cost ~2 us each, ~10 % of the B&B's host time at 64x32 (tools/probes/bnb_profile.py)
     scalar_ptrs = tuple(ctypes.POINTER(t) for t in (ctypes.c_double, ctypes.c_float, ctypes.c_int32, ctypes.c_int64))
     for name in EXPORTS:
+        if name == "nep_debug_block_split":    # (typed at its call, debug_block_split)
+            continue
         fn = getattr(lib, name)
         if fn.argtypes:
             fn.argtypes = [ctypes.c_void_p if t in scalar_ptrs else t for t in fn.argtypes]
@@ -478,6 +480,18 @@ def debug_build(data, variant, step=STEP1, alpha=0.5, soften_step1_sol=1.3, max_
            "nep_debug_build")
     return {"eta": float(eta[0]), "rho": rho, "gam": gam, "rownorm": rn, "R": R, "T": T, "n_int": n_int,
             "n_dual": n_dual}
+
+
+def debug_block_split(n_nodes, n_functions, na, relaxation=RELAX_REFERENCE):
+    """Host-only: how a block of `na` iterating slots is launched (nep_debug_block_split): (slots of the first slot
+    group, 0 = one group; waves per x-pass workgroup over na slots, plain; the same, certificate)."""
+    lib = load_library()
+    # (typed here: an A/B variant library built from an earlier commit loads without this entry point)
+    lib.nep_debug_block_split.argtypes = [ctypes.c_int32] * 4 + [ctypes.c_void_p]
+    out = np.zeros(3, np.int32)
+    _check(lib, lib.nep_debug_block_split(int(n_nodes), int(n_functions), int(relaxation), int(na),
+                                          _ptr(out, ctypes.c_int32)), "nep_debug_block_split")
+    return tuple(int(t) for t in out)
 
 
 def debug_presolve(data, variant, lb, ub, step=STEP1, alpha=0.5, soften_step1_sol=1.3, max_score=0.0,

@@ -607,12 +607,13 @@ __global__ __launch_bounds__(kNodeThreads) void fac_node_pass(DeviceView v, cons
 // (fac_lds_bytes, the dynamic LDS of one workgroup: nep_internal.h, shared with build()'s width check)
 template <int CPL, int TW>
 static hipError_t launch_fac_tw(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init,
-                                bool first, bool plain, int it, hipStream_t s) {
+                                bool first, bool plain, int it, hipStream_t s, int policy_slots) {
   dim3 grid(8 * ((v.F * nslots + 7) / 8)), block(kWave * TW);
   const size_t lds = fac_lds_bytes(TW, v.NP, check);
   const int pl = plain ? 1 : 0;
   // x, its anchor, lambda and its anchor stream once per iteration: non-temporal beyond the Infinity Cache
-  const int nt = (double)nslots * 4.0 * (double)v.sx * sizeof(float) > 160e6 ? 1 : 0;
+  // (policy_slots: every slot iterating beside this launch; launch_x_pass)
+  const int nt = (double)policy_slots * 4.0 * (double)v.sx * sizeof(float) > 160e6 ? 1 : 0;
   if (init) hipLaunchKernelGGL((fac_x_pass<CPL, false, true, false, TW>), grid, block, lds, s, v, slots, pl, it, nslots, nt);
   else if (check)
     hipLaunchKernelGGL((fac_x_pass<CPL, true, false, false, TW>), grid, block, lds, s, v, slots, pl, it, nslots, nt);
@@ -633,23 +634,26 @@ static int fac_tile_waves(const DeviceView &v, int nslots, bool check) {
 
 template <int CPL>
 static hipError_t launch_fac_cpl(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init,
-                                 bool first, bool plain, int it, hipStream_t s) {
+                                 bool first, bool plain, int it, hipStream_t s, int policy_slots) {
   switch (fac_tile_waves(v, nslots, check)) {
-    case 4: return launch_fac_tw<CPL, 4>(v, slots, nslots, check, init, first, plain, it, s);
-    case 8: return launch_fac_tw<CPL, 8>(v, slots, nslots, check, init, first, plain, it, s);
-    case 16: return launch_fac_tw<CPL, 16>(v, slots, nslots, check, init, first, plain, it, s);
+    case 4: return launch_fac_tw<CPL, 4>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 8: return launch_fac_tw<CPL, 8>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 16: return launch_fac_tw<CPL, 16>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
     default: return hipErrorInvalidValue;
   }
 }
 
+// (nep_kernels.hip block_split: the facility model's share of the slot-group rule)
+int fac_block_tile_waves(const DeviceView &v, int nslots, bool check) { return fac_tile_waves(v, nslots, check); }
+
 hipError_t launch_fac_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
-                             bool plain, int it, hipStream_t s) {
+                             bool plain, int it, hipStream_t s, int policy_slots) {
   if (fac_lds_bytes(kMinTileWaves, v.NP, check) > kLdsCap) return hipErrorInvalidValue;
   switch (v.CPL) {
-    case 1: return launch_fac_cpl<1>(v, slots, nslots, check, init, first, plain, it, s);
-    case 2: return launch_fac_cpl<2>(v, slots, nslots, check, init, first, plain, it, s);
-    case 4: return launch_fac_cpl<4>(v, slots, nslots, check, init, first, plain, it, s);
-    case 8: return launch_fac_cpl<8>(v, slots, nslots, check, init, first, plain, it, s);
+    case 1: return launch_fac_cpl<1>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 2: return launch_fac_cpl<2>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 4: return launch_fac_cpl<4>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 8: return launch_fac_cpl<8>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
     default: return hipErrorInvalidValue;
   }
 }

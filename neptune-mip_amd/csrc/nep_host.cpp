@@ -25,7 +25,9 @@
 
 namespace nep {
 hipError_t launch_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
-                         bool plain, int it, hipStream_t s);
+                         bool plain, int it, hipStream_t s, int policy_slots = 0);
+int block_tile_waves(const DeviceView &v, int nslots, bool check);
+int block_split(const DeviceView &v, int na);
 hipError_t launch_node_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
                             bool plain, int it, hipStream_t s);
 hipError_t launch_scalar_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init,
@@ -82,6 +84,8 @@ static const double INF = std::numeric_limits<double>::infinity();
 #define NEP_HALPERN 1
 #endif
 static constexpr bool kHalpern = NEP_HALPERN != 0;
+// slot groups per block unless NEP_BLOCK_GROUPS says otherwise (launch_block; DESIGN.md §6 "Slot groups")
+static constexpr int kBlockGroups = 2;
 
 namespace {
 
@@ -163,6 +167,11 @@ struct Model {
   // — so none of it queues behind the pipelined block on `stream`; ev_aux orders `stream` after it
   hipStream_t aux = nullptr;
   hipEvent_t ev_aux = nullptr;
+  // slot groups (NEP_BLOCK_GROUPS, launch_block): the second group of a block's slots iterates on `grp`, forked
+  // from `stream` (ev_fork) and joined back into it (ev_join) inside the block
+  hipStream_t grp = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  int groups = 1;                   // 1: one chain per block; 2: two slot groups where block_split allows
   DeviceView v{};
   std::vector<void *> allocs;
   double *d_prm = nullptr;      // {tol, cutoff} of the LPs in flight (DeviceView::prm)
@@ -228,6 +237,7 @@ struct Model {
   ~Model() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (aux) (void)hipStreamSynchronize(aux);
+    if (grp) (void)hipStreamSynchronize(grp);
     if (h_ctrl) (void)hipHostFree(h_ctrl);
     if (h_act) (void)hipHostFree(h_act);
     if (h_flows) (void)hipHostFree(h_flows);
@@ -245,6 +255,9 @@ struct Model {
     if (ev1) (void)hipEventDestroy(ev1);
     if (ev_aux) (void)hipEventDestroy(ev_aux);
     if (aux) (void)hipStreamDestroy(aux);
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    if (grp) (void)hipStreamDestroy(grp);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -298,7 +311,7 @@ int build(Model &m, const nep_model_desc &d, bool host_power = true) {
   m.M = d.big_m > 0 ? d.big_m : 1e6;
   m.eps = d.epsilon > 0 ? d.epsilon : 1e-6;
   m.sigma4 = d.step == NEP_STEP2_CREATE ? 1.0 : -1.0;
-  m.NP = (N + 3) / 4 * 4;
+  m.NP = padded_width(N);
   // the widest rows whose certificate pass still fits a CU's LDS at the smallest tile (x_lds_bytes / fac_lds_bytes,
   // nep_internal.h — the launchers' own formula): a wider model could iterate but never launch a certificate
   if (const int np_max = max_padded_width(m.fac); m.NP > np_max)
@@ -306,8 +319,7 @@ int build(Model &m, const nep_model_desc &d, bool host_power = true) {
                                  (m.fac ? "facility" : "reference") + " relaxation's certificate pass holds rows of at most " +
                                  std::to_string(np_max) + " destinations in LDS (largest supported n_nodes: " +
                                  std::to_string(np_max) + ")");
-  const int chunks = m.NP / 4;
-  m.CPL = chunks <= 64 ? 1 : chunks <= 128 ? 2 : chunks <= 256 ? 4 : 8;
+  m.CPL = chunks_per_lane(m.NP);
   m.W.assign(d.workload, d.workload + (size_t)F * N);
   m.cprh.assign(d.core_per_req, d.core_per_req + (size_t)F * N);
   m.wsum.assign(F, 0.0);
@@ -787,6 +799,16 @@ int setup_device(Model &m, int max_batch, void *stream) {
     HIPCHK(hipStreamCreateWithPriority(&m.aux, hipStreamNonBlocking, greatest));
   }
   HIPCHK(hipEventCreateWithFlags(&m.ev_aux, hipEventDisableTiming));
+  // the second slot group's stream (launch_block; NEP_BLOCK_GROUPS=1: one chain per block on `stream` alone, for A/B
+  // — the results are the same bits).  More groups are not offered: each is one more stream on a process's few
+  // hardware queues, of which `stream` and `aux` already take two.
+  m.groups = kBlockGroups;
+  if (const char *e = std::getenv("NEP_BLOCK_GROUPS")) m.groups = std::atoi(e) >= 2 ? 2 : 1;
+  if (m.groups > 1) {
+    HIPCHK(hipStreamCreateWithFlags(&m.grp, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&m.ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&m.ev_join, hipEventDisableTiming));
+  }
   DeviceView &v = m.v;
   v.N = m.N; v.NP = m.NP; v.F = m.F; v.R = m.R; v.JB = m.JB; v.CPL = m.CPL;
   v.has_n = m.has_n; v.step2 = m.step2; v.variant = m.variant; v.fac = m.fac;
@@ -1608,29 +1630,65 @@ int submit(Model &m, int n, const int32_t *slots, const double *lbi, const doubl
   return NEP_OK;
 }
 
+// Iterations [it0, it1) of a block on `n` of its `na` iterating slots, one launch chain on `s`.  (The x pass takes
+// its non-temporal policy from na: speed only, and the one the launch over the whole block would get.)
+hipError_t launch_iters(Model &m, const int32_t *slots, int n, int na, int it0, int it1, hipStream_t s) {
+  const int ce = m.run.check_every;
+  hipError_t e = hipSuccess;
+  for (int it = it0; it < it1 && e == hipSuccess; ++it) {
+    const bool check = it == 0, first = it == 1;
+    const bool plain = !kHalpern || ce < 4 || it == 0 || it == ce - 1;
+    e = launch_x_pass(m.v, slots, n, check, false, first, plain, it, s, na);
+    if (e == hipSuccess) e = launch_node_pass(m.v, slots, n, check, false, first, plain, it, s);
+    if (e == hipSuccess && (m.step2 || check)) e = launch_scalar_pass(m.v, slots, n, check, false, first, plain, it, ce, s);
+  }
+  return e;
+}
+
+// Iterations [it0, it1) of a block: one chain on `stream` (nA == 0), or its two slot groups side by side — group A,
+// d_slots[0 .. nA), on `stream` and group B, d_slots[nA .. na), on `grp` — so that one group's node and scalar passes
+// and the part-empty tail of its x pass run under the other group's x pass.  No kernel of an iteration reads another
+// slot's state, so the groups need no order between them, and with block_split's rule every launch of a group runs
+// the kernel variant the launch over all na slots runs: each LP's arithmetic, and so its bits, stay what they were.
+// Ordering.  B forks from `stream` (ev_fork) behind the d_slots upload and behind every wait for a submit's
+// initialisation (ev_aux) that `stream` holds, so B iterates initialised slots from the list A reads.  B joins
+// (ev_join) before this returns, i.e. before the block's Ctrl copy and before anything later on `stream`: once
+// advance has waited for `stream`, the slots of both groups are complete, their Ctrl is the copied one, and the reads
+// of finished slots on `aux` that follow see them whole.  The join is enqueued even after a failed launch, so that a
+// stream capture never ends with `grp` still forked.
+hipError_t launch_span(Model &m, int na, int nA, int it0, int it1) {
+  if (it0 >= it1) return hipSuccess;
+  if (!nA) return launch_iters(m, m.d_slots, na, na, it0, it1, m.stream);
+  hipError_t e = hipEventRecord(m.ev_fork, m.stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(m.grp, m.ev_fork, 0);
+  if (e != hipSuccess) return e;
+  const hipError_t ea = launch_iters(m, m.d_slots, nA, na, it0, it1, m.stream);
+  const hipError_t eb = launch_iters(m, m.d_slots + nA, na - nA, na, it0, it1, m.grp);
+  e = hipEventRecord(m.ev_join, m.grp);
+  if (e == hipSuccess) e = hipStreamWaitEvent(m.stream, m.ev_join, 0);
+  return ea != hipSuccess ? ea : eb != hipSuccess ? eb : e;
+}
+
+void drop_block_graphs(Model &m) {
+  for (hipGraphExec_t &g : m.block_graph)
+    if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+  m.block_graph.assign(m.max_batch + 1, nullptr);
+}
+
 // The launches of one block (iterations 0 .. ce-1 on `na` iterating slots, m.d_slots) captured
 // once as a HIP graph and cached per na; m.d_slots is read by the kernels at run time, so the
-// graph replays for any set of na slots.
-hipError_t block_graph(Model &m, int na, hipGraphExec_t *out) {
+// graph replays for any set of na slots.  With slot groups (nA > 0; a function of na while m.groups holds) the
+// graph has two parallel branches between the fork and the join.
+hipError_t block_graph(Model &m, int na, int nA, hipGraphExec_t *out) {
   const int ce = m.run.check_every;
   if (m.graph_ce != ce) {
-    for (hipGraphExec_t &g : m.block_graph)
-      if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    m.block_graph.assign(m.max_batch + 1, nullptr);
+    drop_block_graphs(m);
     m.graph_ce = ce;
   }
   if (!m.block_graph[na]) {
     hipError_t e = hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) return e;
-    hipError_t le = hipSuccess;
-    for (int it = 0; it < ce && le == hipSuccess; ++it) {
-      const bool check = it == 0, first = it == 1;
-      const bool plain = !kHalpern || ce < 4 || it == 0 || it == ce - 1;
-      le = launch_x_pass(m.v, m.d_slots, na, check, false, first, plain, it, m.stream);
-      if (le == hipSuccess) le = launch_node_pass(m.v, m.d_slots, na, check, false, first, plain, it, m.stream);
-      if (le == hipSuccess && (m.step2 || check))
-        le = launch_scalar_pass(m.v, m.d_slots, na, check, false, first, plain, it, ce, m.stream);
-    }
+    const hipError_t le = launch_span(m, na, nA, 0, ce);
     hipGraph_t graph = nullptr;
     e = hipStreamEndCapture(m.stream, &graph);
     if (le != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); return le; }
@@ -1652,7 +1710,8 @@ hipError_t block_graph(Model &m, int na, hipGraphExec_t *out) {
 // Halpern steps.  Every 4th block runs eagerly with one steady-state x-pass launch bracketed by HIP
 // events on the model's stream (nep_get_stats); the others replay the block's launches as one HIP
 // graph (a block is 2-3 launches per iteration: at small sizes the iteration is launch-latency
-// bound).  The block ends with an async copy of every slot's Ctrl into pinned host memory.
+// bound).  Where block_split allows, the slots iterate as two groups on two streams (launch_span), in the graph as
+// two parallel branches.  The block ends with an async copy of every slot's Ctrl into pinned host memory.
 int launch_block(Model &m) {
   DeviceView &v = m.v;
   const int ce = m.run.check_every;
@@ -1665,29 +1724,44 @@ int launch_block(Model &m) {
   // host buffer that the caller's next submit may reallocate (round-3 ADVICE)
   std::copy(m.act.begin(), m.act.end(), m.h_act);
   HIPCHK(hipMemcpyAsync(m.d_slots, m.h_act, na * sizeof(int32_t), hipMemcpyHostToDevice, m.stream));
+  // slot groups (launch_span): the rule is the launchers' own (nep_kernels.hip block_split)
+  int nA = m.groups > 1 ? block_split(v, na) : 0;
   bool eager = sample_it >= 0 || !m.graphs_ok;
   if (!eager) {
     hipGraphExec_t g = nullptr;
-    if (block_graph(m, na, &g) != hipSuccess) {
+    hipError_t e = block_graph(m, na, nA, &g);
+    if (e != hipSuccess && nA) {
+      // the forked capture or its instantiation failed: this model's blocks stay on one stream from here on
+      (void)hipGetLastError();
+      m.groups = 1;
+      nA = 0;
+      drop_block_graphs(m);
+      e = block_graph(m, na, 0, &g);
+    }
+    if (e != hipSuccess) {
       (void)hipGetLastError();
       m.graphs_ok = false;   // e.g. a caller's stream that cannot be captured
       eager = true;
     } else {
       HIPCHK(hipGraphLaunch(g, m.stream));
-      m.stats.x_pass_launches += ce;
     }
   }
-  for (int it = 0; it < ce && eager; ++it) {
-    const bool check = it == 0, first = it == 1;
-    const bool plain = !kHalpern || ce < 4 || it == 0 || it == ce - 1;
-    const bool sample = it == sample_it;
-    if (sample) HIPCHK(hipEventRecord(m.ev0, m.stream));
-    HIPCHK(launch_x_pass(v, m.d_slots, na, check, false, first, plain, it, m.stream));
-    if (sample) HIPCHK(hipEventRecord(m.ev1, m.stream));
-    HIPCHK(launch_node_pass(v, m.d_slots, na, check, false, first, plain, it, m.stream));
-    if (m.step2 || check) HIPCHK(launch_scalar_pass(v, m.d_slots, na, check, false, first, plain, it, ce, m.stream));
-    m.stats.x_pass_launches += 1;
+  if (eager) {
+    // the sampled iteration is one x-pass launch over all na slots, alone on the device between its events
+    // (nep_get_stats keeps its meaning): the groups join in front of it and fork again behind its node pass
+    const int s0 = sample_it >= 0 ? sample_it : ce, s1 = sample_it >= 0 ? sample_it + 1 : ce;
+    HIPCHK(launch_span(m, na, nA, 0, s0));
+    if (sample_it >= 0) {
+      const bool plain = !kHalpern;   // (ce >= 4 and 0 < sample_it < ce - 1: a steady-state iteration)
+      HIPCHK(hipEventRecord(m.ev0, m.stream));
+      HIPCHK(launch_x_pass(v, m.d_slots, na, false, false, false, plain, sample_it, m.stream));
+      HIPCHK(hipEventRecord(m.ev1, m.stream));
+      HIPCHK(launch_node_pass(v, m.d_slots, na, false, false, false, plain, sample_it, m.stream));
+      if (m.step2) HIPCHK(launch_scalar_pass(v, m.d_slots, na, false, false, false, plain, sample_it, ce, m.stream));
+    }
+    HIPCHK(launch_span(m, na, nA, s1, ce));
   }
+  m.stats.x_pass_launches += ce;   // (iterations, whichever way they were launched)
   HIPCHK(hipMemcpyAsync(m.h_ctrl, v.ctrl, sizeof(Ctrl) * m.max_batch, hipMemcpyDeviceToHost, m.stream));
   m.stats.lp_iterations += (int64_t)na * ce;
   m.launched = m.act;
@@ -2499,6 +2573,21 @@ int nep_debug_build(const nep_model_desc *desc, double *eta, double *rho, double
   if (dims) {
     dims[0] = m.R; dims[1] = m.F; dims[2] = m.il.n_int; dims[3] = m.dl.n_dual;
   }
+  return NEP_OK;
+}
+
+int nep_debug_block_split(int32_t n_nodes, int32_t n_functions, int32_t relaxation, int32_t na, int32_t *out3) {
+  if (!out3 || n_nodes < 1 || n_functions < 1 || na < 1) return fail(NEP_ERR_ARG, "bad argument");
+  DeviceView v{};
+  v.N = n_nodes;
+  v.F = n_functions;
+  v.fac = relaxation == NEP_RELAX_FACILITY ? 1 : 0;
+  v.NP = padded_width(n_nodes);
+  if (v.NP > max_padded_width(v.fac != 0)) return fail(NEP_ERR_ARG, "n_nodes beyond the widest supported row");
+  v.CPL = chunks_per_lane(v.NP);
+  out3[0] = block_split(v, na);
+  out3[1] = block_tile_waves(v, na, false);
+  out3[2] = block_tile_waves(v, na, true);
   return NEP_OK;
 }
 

@@ -108,6 +108,13 @@ NEP_HD inline size_t fac_lds_bytes(int tw, int NP, bool check) {
   const int sw = check ? 2 : 1;
   return (size_t)(sw * tw + tw + (check ? tw : 0) + 3) * NP * sizeof(float) + 3 * (size_t)NP * sizeof(double);
 }
+// a routing row of N destinations: its padded width NP (16-byte chunks of 4) and the chunks each of a wave's 64
+// lanes owns (CPL, the x pass's template width)
+inline int padded_width(int N) { return (N + 3) / 4 * 4; }
+inline int chunks_per_lane(int NP) {
+  const int chunks = NP / 4;
+  return chunks <= 64 ? 1 : chunks <= 128 ? 2 : chunks <= 256 ? 4 : 8;
+}
 // the largest padded width NP (a multiple of 4) whose certificate pass fits the cap at kMinTileWaves
 inline int max_padded_width(bool fac) {
   int np = 4;

@@ -1701,12 +1701,13 @@ __global__ void node_bounds_scatter(DeviceView v, const int32_t *__restrict__ sl
 // ------------------------------------------------------------------------------------------
 template <int CPL, int TW>
 static hipError_t launch_x_tw(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init,
-                              bool first, bool plain, int it, hipStream_t s) {
+                              bool first, bool plain, int it, hipStream_t s, int policy_slots) {
   dim3 grid(8 * ((v.F * nslots + 7) / 8)), block(kWave * TW);
   const size_t lds = x_lds_bytes(TW, v.NP, check);
   const int pl = plain ? 1 : 0;
-  // non-temporal routing streams only when the iterating slots' x + anchor exceed ~160 MB (see ld_x4)
-  const int nt = (double)nslots * 2.0 * (double)v.sx * sizeof(float) > 160e6 ? 1 : 0;
+  // non-temporal routing streams only when the iterating slots' x + anchor exceed ~160 MB (see ld_x4);
+  // policy_slots: every slot iterating beside this launch, those of the block's other slot group included
+  const int nt = (double)policy_slots * 2.0 * (double)v.sx * sizeof(float) > 160e6 ? 1 : 0;
   if (init) hipLaunchKernelGGL((x_pass<CPL, false, true, false, TW>), grid, block, lds, s, v, slots, pl, it, nslots, nt);
   else if (check)
     hipLaunchKernelGGL((x_pass<CPL, true, false, false, TW>), grid, block, lds, s, v, slots, pl, it, nslots, nt);
@@ -1732,32 +1733,57 @@ static int tile_waves(const DeviceView &v, int nslots, bool check) {
   return tw;
 }
 
+int fac_block_tile_waves(const DeviceView &v, int nslots, bool check);   // (nep_fac.hip fac_tile_waves)
+
+// waves per x-pass workgroup of a launch over `nslots` slots, plain or certificate variant, either relaxation
+int block_tile_waves(const DeviceView &v, int nslots, bool check) {
+  return v.fac ? fac_block_tile_waves(v, nslots, check) : tile_waves(v, nslots, check);
+}
+
+// Slot groups of a block (nep_host.cpp launch_block): the `na` iterating slots may run as two groups of
+// nA = ceil(na / 2) and na - nA slots on two streams — the slots are independent LPs — but only where every x-pass
+// launch of a group has the waves per workgroup the launch over all na slots has, plain and certificate variant
+// alike: the tile fixes the order of the column sums (above), so only then does each LP keep its bits.  Returns nA,
+// or 0: one group.  (At F = 256 the halves need 4 slots each: na >= 8.  The root LP and a draining batch stay whole.)
+int block_split(const DeviceView &v, int na) {
+  if (na < 2) return 0;
+  const int nA = (na + 1) / 2, nB = na - nA;
+  for (int check = 0; check < 2; ++check) {
+    const int tw = block_tile_waves(v, na, check != 0);
+    if (block_tile_waves(v, nA, check != 0) != tw || block_tile_waves(v, nB, check != 0) != tw) return 0;
+  }
+  return nA;
+}
+
 template <int CPL>
 static hipError_t launch_x_cpl(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init,
-                               bool first, bool plain, int it, hipStream_t s) {
+                               bool first, bool plain, int it, hipStream_t s, int policy_slots) {
   switch (tile_waves(v, nslots, check)) {
-    case 4: return launch_x_tw<CPL, 4>(v, slots, nslots, check, init, first, plain, it, s);
-    case 8: return launch_x_tw<CPL, 8>(v, slots, nslots, check, init, first, plain, it, s);
-    case 16: return launch_x_tw<CPL, 16>(v, slots, nslots, check, init, first, plain, it, s);
+    case 4: return launch_x_tw<CPL, 4>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 8: return launch_x_tw<CPL, 8>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 16: return launch_x_tw<CPL, 16>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
     default: return hipErrorInvalidValue;
   }
 }
 
 hipError_t launch_fac_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
-                             bool plain, int it, hipStream_t s);
+                             bool plain, int it, hipStream_t s, int policy_slots);
 hipError_t launch_fac_node_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
                                 bool plain, int it, hipStream_t s);
 
+// policy_slots: the slot count behind the non-temporal policy when the launch covers one slot group of a block
+// (block_split below) — the whole block's, so a group streams as the unsplit launch would; 0: nslots
 hipError_t launch_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
-                         bool plain, int it, hipStream_t s) {
-  if (v.fac) return launch_fac_x_pass(v, slots, nslots, check, init, first, plain, it, s);   // (nep_fac.hip)
+                         bool plain, int it, hipStream_t s, int policy_slots) {
+  if (policy_slots <= 0) policy_slots = nslots;
+  if (v.fac) return launch_fac_x_pass(v, slots, nslots, check, init, first, plain, it, s, policy_slots);   // (nep_fac.hip)
   // (build() admits no such width; a view from elsewhere fails here instead of at the launch)
   if (x_lds_bytes(kMinTileWaves, v.NP, check) > kLdsCap) return hipErrorInvalidValue;
   switch (v.CPL) {
-    case 1: return launch_x_cpl<1>(v, slots, nslots, check, init, first, plain, it, s);
-    case 2: return launch_x_cpl<2>(v, slots, nslots, check, init, first, plain, it, s);
-    case 4: return launch_x_cpl<4>(v, slots, nslots, check, init, first, plain, it, s);
-    case 8: return launch_x_cpl<8>(v, slots, nslots, check, init, first, plain, it, s);
+    case 1: return launch_x_cpl<1>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 2: return launch_x_cpl<2>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 4: return launch_x_cpl<4>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
+    case 8: return launch_x_cpl<8>(v, slots, nslots, check, init, first, plain, it, s, policy_slots);
     default: return hipErrorInvalidValue;
   }
 }
