@@ -34,6 +34,8 @@
 extern "C" {
 #endif
 
+/* (the fixed-placement evaluator below adds entry points only: no existing call or layout changes, so the version
+ * that callers and the suite pin stays 13) */
 #define NEP_API_VERSION 13
 
 /* variants: neptune.py:41-66 (NeptuneMinDelay / MinUtilization / MinDelayAndUtilization) */
@@ -234,6 +236,52 @@ int nep_lp_routing_entries(void *model, int32_t slot, double threshold, int32_t 
 int nep_lp_allocation_entries(void *model, int32_t slot, double threshold, int64_t capacity, int64_t *n_entries,
                               int32_t *fn, int32_t *dst);
 
+/* The fixed-placement evaluator (csrc/nep_leaf.hip, csrc/nep_leaf_repair.cpp; DESIGN.md §7 "Fixed-placement
+ * evaluator"), step-1 reference-relaxation models of every variant.  A leaf fixes every c and n; its LP is then one
+ * routing simplex per row (C4) coupled by the N CPU rows (C5) and the column floors (C2) only.  For each of the n
+ * placements z_leaf[b] (every c and n 0 or 1):
+ *   lower[b]   the best value over rounds 0 .. opts->rounds of the Lagrangian that prices C5 with y >= 0 and drops C2,
+ *                L(y) = cost_n sum n + sum_rows min_{j open for f} (obj_r D[src_r, j] + y_j W[f, i] cpr[f, j]) - sum_j y_j cores_j
+ *              over the loaded routing rows, in fp64 from the instance's fp64 D / W / cpr and the objective's
+ *              coefficients in reference units: a valid lower bound on the leaf LP at every y.  Round 0 uses prices_in
+ *              (NULL: zeros); the later rounds take subgradient steps (nep_leaf.h).  Rounds run on the device, on the
+ *              model's auxiliary stream, without touching any slot; no float atomics (two calls on the same input
+ *              return the same bits).
+ *   upper[b]   the objective of a routing that meets every reference step-1 row at the placement (C2 at 1 - epsilon,
+ *              the pooled row's mass spent on the loaded flow's deficits; C5 at CPU_j <= cores_j), repaired on the
+ *              host from the round-0 assignment; +inf when none was found (chained moves are not tried)
+ *   status[b]  NEP_LEAF_INFEASIBLE: a row without x rejects the placement (C3 memory, C6/C7 n against c, C8, a function
+ *              with no open destination; lower = upper = +inf); NEP_LEAF_CUTOFF: lower >= opts->cutoff (the placement's
+ *              rounds stop early, no routing is sought); NEP_LEAF_EXACT: upper - lower <= tol max(1, |lower|);
+ *              NEP_LEAF_FEASIBLE: a routing with a wider bracket; NEP_LEAF_NO_POINT: the bound only
+ *   prices_out [n][N] (or NULL) the prices behind lower; cpu [n][N] (or NULL) the CPU loads of the returned routing, or
+ *              of the last round's assignment when there is none
+ * Any n >= 1 (chunked over a workspace allocated on the first call; a model that never calls the evaluator allocates
+ * and launches nothing for it).  That first call allocates and uploads with blocking calls: LPs in flight keep their
+ * results but wait for it, so a caller that streams LPs makes its first call before it submits.  NEP_ERR_ARG: a step-2 or facility-relaxation model, an entry that is not 0 or 1, a
+ * negative price, a NULL required argument.  opts NULL: 32 rounds, no cutoff, tol 1e-6. */
+enum { NEP_LEAF_EXACT = 0, NEP_LEAF_FEASIBLE = 1, NEP_LEAF_NO_POINT = 2, NEP_LEAF_INFEASIBLE = 3, NEP_LEAF_CUTOFF = 4 };
+typedef struct {
+  int32_t rounds;              /* price rounds after round 0 */
+  double cutoff;               /* +inf: none */
+  double tol;                  /* NEP_LEAF_EXACT's relative bracket (0: 1e-6) */
+} nep_leaf_opts;
+int nep_leaf_eval(void *model, int32_t n, const double *z_leaf /* [n][n_int] */, const nep_leaf_opts *opts,
+                  const double *prices_in /* [n][N] >= 0, or NULL */, double *lower, double *upper, int32_t *status,
+                  double *prices_out /* [n][N] or NULL */, double *cpu /* [n][N] or NULL */);
+/* the routing behind upper[k] of the last nep_leaf_eval call, in nep_lp_routing_entries' format and order (rows of
+ * nep_lp_get_rows, row-major, ascending destination; a pooled row's value is per source), unrounded; count-only when
+ * capacity is too small.  NEP_ERR_STATE for a placement without a routing. */
+int nep_leaf_routing_entries(void *model, int32_t k, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst,
+                             double *val);
+/* host-only (no device work): the evaluator's repair of one placement from an assignment asg [R] (a destination per
+ * loaded routing row of the model's row layout, e.g. the nearest open one); *found = 0 / 1, *upper, the entries as
+ * nep_leaf_routing_entries returns them (count-only when capacity is too small), cpu [N] (may be NULL).  Lets the CPU
+ * test-suite check the repair without a GPU. */
+int nep_debug_leaf_repair(const nep_model_desc *desc, const double *z_leaf, const int32_t *asg, double *upper,
+                          int32_t *found, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst, double *val,
+                          double *cpu);
+
 /* The reference's offline scorers and feasibility checkers on a slot's solution, on the device
  * (efttc/utils/objectives.py:23-98, efttc/utils/constraints_step1.py:5-133; booleans are the
  * reference's truthiness, value != 0).  out[NEP_SC_COUNT]: */
@@ -336,6 +384,10 @@ typedef struct {
   int64_t strong_iters;            /* branching 2: iteration budget of a probe LP */
   double objective_unit;           /* with objective_integral: the objective's integral unit (<= 0: 1) — e.g. alpha / N
                                       for MinDelayAndUtilization without workload, whose objective is alpha / N sum n */
+  int32_t leaf_eval;               /* 1 = queued leaves and retries go through the fixed-placement evaluator in one call
+                                      before their LPs are submitted (needs the leaf engine's evaluator pair, see
+                                      nep_bnb_set_leaf_engine; single rank only); 0 (default): off */
+  int32_t leaf_rounds;             /* the evaluator's price rounds per call (<= 0: 32) */
 } nep_bnb_params;
 
 typedef struct {
@@ -345,7 +397,8 @@ typedef struct {
   int64_t advance_calls, inflight_sum, lp_incumbents, heuristic_incumbents, n_lp_iters;
   double advance_seconds, finish_seconds, submit_seconds, drain_seconds, root_seconds;
   double bound, incumbent;         /* at the end: best proven bound, incumbent value (+inf: none) */
-  int32_t incumbent_source;        /* 0 none, 1 a certified leaf LP, 2 nep_bnb_set_incumbent */
+  int32_t incumbent_source;        /* 0 none, 1 a certified leaf LP, 2 nep_bnb_set_incumbent, 3 a routing of the
+                                      fixed-placement evaluator (nep_bnb_incumbent_routing) */
   int32_t incumbent_slot;          /* leaf-model slot holding the incumbent LP's state (source 1) */
   int32_t limit_hit, any_unresolved, unresolved_below;
   int32_t stalled;                 /* API 12: ended because open nodes could never get a slot (reported as a limit) */
@@ -432,9 +485,37 @@ int nep_bnb_import_nodes(void *tree, int32_t k, const int32_t *lens, const doubl
                          const double *val);
 int nep_bnb_get_stats(void *tree, nep_bnb_stats *out);
 int nep_bnb_get_lp_iters(void *tree, int64_t *out);
-/* the LP incumbent's integer vector (n_int) and its leaf box (at most c1 - c0 + n1 - n0 entries: a leaf fixes every
- * c and n; *n_fix = -1: no LP incumbent) */
+/* the LP incumbent's (source 1) or the evaluator incumbent's (source 3) integer vector (n_int) and its leaf box (at most
+ * c1 - c0 + n1 - n0 entries: a leaf fixes every c and n; *n_fix = -1: neither) */
 int nep_bnb_incumbent(void *tree, double *z_int, int32_t *n_fix, int32_t *idx, double *val);
+
+/* The tree's use of the fixed-placement evaluator (params.leaf_eval = 1).  Before leaves or retries are
+ * submitted, the queued ones that fix every c and n are evaluated in one call at the current cutoff: INFEASIBLE or CUTOFF
+ * drops the leaf with no LP; a finite `upper` below the incumbent (beyond the gap) becomes the incumbent (source 3: the
+ * tree keeps z and the entries, the new cutoff goes to every model); EXACT resolves the leaf; FEASIBLE or NO_POINT
+ * raises the leaf's bound to max(own, lower) and its LP is submitted as before if that is still below the cutoff.
+ * The evaluator pair is the leaf engine's: nep_bnb_create sets nep_leaf_eval / nep_leaf_routing_entries of a step-1
+ * reference model; a caller with its own engines sets its pair here (before the first nep_bnb_run).  A NULL pair, or
+ * leaf_eval = 0, gives the search without the evaluator.  (The pair and the counters live beside nep_bnb_engine and
+ * nep_bnb_stats, whose layouts stay as they are.) */
+typedef int (*nep_bnb_leaf_eval_fn)(void *ctx, int32_t n, const double *z_leaf, const nep_leaf_opts *opts,
+                                    const double *prices_in, double *lower, double *upper, int32_t *status,
+                                    double *prices_out, double *cpu);
+typedef int (*nep_bnb_leaf_routing_fn)(void *ctx, int32_t k, int64_t capacity, int64_t *n_entries, int32_t *row,
+                                       int32_t *dst, double *val);
+int nep_bnb_set_leaf_engine(void *tree, void *ctx, nep_bnb_leaf_eval_fn leaf_eval,
+                            nep_bnb_leaf_routing_fn leaf_routing_entries);
+typedef struct {
+  int64_t leaf_eval_calls, leaf_eval_leaves;   /* evaluator calls, leaves evaluated */
+  int64_t leaf_eval_exact, leaf_eval_feasible; /* leaves resolved EXACT; FEASIBLE (their LP still runs) */
+  int64_t leaf_eval_dropped;                   /* leaves dropped with no LP (INFEASIBLE, CUTOFF, bound at the cutoff) */
+  int64_t leaf_eval_incumbents;
+  double leaf_eval_seconds;
+} nep_bnb_leaf_stats;
+int nep_bnb_get_leaf_stats(void *tree, nep_bnb_leaf_stats *out);
+/* the entries of the evaluator incumbent (source 3), as nep_leaf_routing_entries returns them; count-only when capacity
+ * is too small; *n_entries = -1 when the incumbent has another source */
+int nep_bnb_incumbent_routing(void *tree, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst, double *val);
 
 const char *nep_last_error(void);
 int nep_api_version(void);

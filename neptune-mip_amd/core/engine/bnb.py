@@ -102,6 +102,8 @@ class BnBResult:
         self.native = False             # the search ran on the native tree (csrc/nep_bnb.cpp)
         self.strong = None              # (native, branching 2) strong-branching probe counts
         self.rc = None                  # (native) reduced-cost fixing: variables fixed, calls, children / leaves cut
+        self.leaf_stats = None          # (native) fixed-placement evaluator: nep_bnb_leaf_stats as a dict
+        self.incumbent_source = 0       # (native) 0 none, 1 a leaf LP, 2 a heuristic point, 3 the evaluator's routing
 
     def as_dict(self):
         d = {k: getattr(self, k) for k in ("status", "objective", "bound", "nodes", "leaves", "lps", "certified",
@@ -162,7 +164,7 @@ class BranchAndBound:
                  trace=None, rebalance_every=8, primal=None, primal_every=0,
                  leaf_routing_warm=False, root_check_every=64, objective_integral=False, warm_weight_ref=0.0,
                  native=None, step2_native=None, branching=0, strong_cands=8, strong_rel=2, strong_iters=256,
-                 rc_fixing=False):
+                 rc_fixing=False, leaf_eval=False, leaf_rounds=32):
         self.lp = lp
         self.two = bound_lp is not None
         self.N, self.F = lp.N, lp.F
@@ -236,6 +238,12 @@ class BranchAndBound:
         # shows that moving it costs more than the pruning cutoff (nep_lp_rc_fixings).  Off by default.
         self.rc_fixing = bool(rc_fixing)
         self._rc_warned = False
+        # fixed-placement evaluator (native tree; DESIGN.md §7 "Fixed-placement evaluator"): queued leaves go through
+        # the leaf model's leaf_eval in one call before their LPs are submitted — dropped, resolved, made the
+        # incumbent (BnBResult.incumbent_source 3) or given a better bound.  Off by default.
+        self.leaf_eval = bool(leaf_eval)
+        self.leaf_rounds = int(leaf_rounds)
+        self._leaf_warned = False
         # (the leaf / reference model only — the model whose node LPs the replay measured; the facility relaxation
         # keeps the parent-relative band: 256x128 / 20 s gap 0.51 % with it, 0.82 % with the band on both)
         for m_ in (lp,):
@@ -826,7 +834,7 @@ class BranchAndBound:
         """solve() on the native tree (nep_bnb_*, csrc/nep_bnb.cpp): the same search, its loop in the library;
         this method handles the root's primal heuristic (NEP_BNB_ROOT) and the end (routing, polish, repair)."""
         import ctypes
-        from .lp import BnbParams, BnbStats, PyBnbEngine, _check, _ptr, load_library
+        from .lp import BnbParams, BnbStats, LeafStats, PyBnbEngine, _check, _ptr, load_library
         t0 = self.t0 = time.time()
         self.res = res = BnBResult()
         comm = self.comm
@@ -847,7 +855,8 @@ class BranchAndBound:
                       node_limit=int(min(float(self.node_limit), 2.0 ** 62)), time_limit=float(self.time_limit or 0.0),
                       world=int(comm.world), rank=int(comm.rank), branching=self.branching,
                       strong_cands=self.strong_cands, strong_rel=self.strong_rel, strong_iters=self.strong_iters,
-                      rc_fixing=1 if self.rc_fixing else 0, objective_unit=float(self.objective_unit))
+                      rc_fixing=1 if self.rc_fixing else 0, objective_unit=float(self.objective_unit),
+                      leaf_eval=1 if self.leaf_eval else 0, leaf_rounds=int(self.leaf_rounds))
         py_engines = []
         if hasattr(lp, "_h"):
             tree = lib.nep_bnb_create(lp._h, self.bound_lp._h if self.two else None, ctypes.byref(p),
@@ -860,6 +869,8 @@ class BranchAndBound:
                                               ctypes.byref(p), _ptr(self.fn_mem), _ptr(self.node_mem))
         if not tree:
             raise RuntimeError(f"nep_bnb_create failed: {lib.nep_last_error().decode()}")
+        if py_engines and py_engines[0].leaf_pair is not None:
+            _check(lib, lib.nep_bnb_set_leaf_engine(tree, None, *py_engines[0].leaf_pair), "nep_bnb_set_leaf_engine")
 
         def run_checked(what, rc):
             for e in py_engines:
@@ -949,8 +960,31 @@ class BranchAndBound:
                 res.incumbent_slot = int(st.incumbent_slot)
                 k = n_fix.value
                 self.inc_node = _Node(st.incumbent, idx[:k].astype(np.int64), val[:k].copy(), LEAF, None, 0)
+            elif st.incumbent_source == 3:
+                # the evaluator's routing: z, the leaf box and the entries are the tree's (no slot holds them)
+                n_fix = ctypes.c_int32()
+                z = np.zeros(lp.n_int)
+                idx = np.zeros(self._nb + 1, np.int32)
+                val = np.zeros(self._nb + 1)
+                _check(lib, lib.nep_bnb_incumbent(tree, _ptr(z), ctypes.byref(n_fix), _ptr(idx), _ptr(val)),
+                       "nep_bnb_incumbent")
+                cnt = ctypes.c_int64()
+                _check(lib, lib.nep_bnb_incumbent_routing(tree, 0, ctypes.byref(cnt), None, None, None),
+                       "nep_bnb_incumbent_routing")
+                row, dst = np.zeros(cnt.value, np.int32), np.zeros(cnt.value, np.int32)
+                ev = np.zeros(cnt.value)
+                _check(lib, lib.nep_bnb_incumbent_routing(tree, cnt.value, ctypes.byref(cnt), _ptr(row), _ptr(dst),
+                                                          _ptr(ev)), "nep_bnb_incumbent_routing")
+                res.objective, res.z, res.incumbent_slot = float(st.incumbent), z, None
+                res.x = lp.routing_from_entries(row, dst, ev)
+                k = n_fix.value
+                self.inc_node = _Node(st.incumbent, idx[:k].astype(np.int64), val[:k].copy(), LEAF, None, 0)
             elif st.incumbent_source == 0:
                 res.objective = None
+            res.incumbent_source = int(st.incumbent_source)
+            ls = LeafStats()
+            _check(lib, lib.nep_bnb_get_leaf_stats(tree, ctypes.byref(ls)), "nep_bnb_get_leaf_stats")
+            res.leaf_stats = {k: getattr(ls, k) for k, _ in LeafStats._fields_}
         finally:
             lib.nep_bnb_destroy(tree)
         names = ("certified", "bound", "limit", "infeasible", "cutoff", "numerical", "presolve_infeasible")
@@ -1006,6 +1040,9 @@ class BranchAndBound:
         if self.rc_fixing and not self._rc_warned:
             self._rc_warned = True
             warnings.warn("rc_fixing is a feature of the native tree search: this module's loop ignores it")
+        if self.leaf_eval and not self._leaf_warned:
+            self._leaf_warned = True
+            warnings.warn("leaf_eval is a feature of the native tree search: this module's loop ignores it")
         t0 = self.t0 = time.time()
         self.res = res = BnBResult()
         lp = self.lp

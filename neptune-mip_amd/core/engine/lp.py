@@ -20,6 +20,7 @@ VARIANTS = {"MinDelay": MIN_DELAY, "MinUtilization": MIN_UTILIZATION,
             "MinDelayAndUtilization": MIN_DELAY_AND_UTILIZATION}
 API_VERSION = 13
 RELAX_REFERENCE, RELAX_FACILITY = 0, 1
+LEAF_EXACT, LEAF_FEASIBLE, LEAF_NO_POINT, LEAF_INFEASIBLE, LEAF_CUTOFF = 0, 1, 2, 3, 4
 
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -47,6 +48,10 @@ class LpOpts(ctypes.Structure):
                 ("polish_after", ctypes.c_double), ("bound_res", ctypes.c_double)]
 
 
+class LeafOpts(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_int32), ("cutoff", ctypes.c_double), ("tol", ctypes.c_double)]
+
+
 class ModelInfo(ctypes.Structure):
     _fields_ = [("n_int", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_tiles", ctypes.c_int32),
                 ("max_batch", ctypes.c_int32), ("x_entries", ctypes.c_int64), ("bytes_per_iter", ctypes.c_int64),
@@ -72,7 +77,15 @@ class BnbParams(ctypes.Structure):
                 ("node_limit", ctypes.c_int64), ("time_limit", ctypes.c_double),
                 ("world", ctypes.c_int32), ("rank", ctypes.c_int32), ("branching", ctypes.c_int32),
                 ("strong_cands", ctypes.c_int32), ("strong_rel", ctypes.c_int32), ("rc_fixing", ctypes.c_int32),
-                ("strong_iters", ctypes.c_int64), ("objective_unit", ctypes.c_double)]
+                ("strong_iters", ctypes.c_int64), ("objective_unit", ctypes.c_double),
+                ("leaf_eval", ctypes.c_int32), ("leaf_rounds", ctypes.c_int32)]
+
+
+class LeafStats(ctypes.Structure):
+    """nep_bnb_leaf_stats: the native tree's use of the fixed-placement evaluator"""
+    _fields_ = [(k, ctypes.c_int64) for k in ("leaf_eval_calls", "leaf_eval_leaves", "leaf_eval_exact",
+                                              "leaf_eval_feasible", "leaf_eval_dropped", "leaf_eval_incumbents")] + \
+               [("leaf_eval_seconds", ctypes.c_double)]
 
 
 class BnbStats(ctypes.Structure):
@@ -112,6 +125,10 @@ BNB_SUBMIT_EX = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, 
                                  ctypes.POINTER(LpOpts), _i64p, _dblp, _i32p)
 BNB_RC_FIX = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int64, _i64p,
                               _i32p, _dblp)
+BNB_LEAF_EVAL = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, _dblp, ctypes.POINTER(LeafOpts), _dblp,
+                                 _dblp, _dblp, _i32p, _dblp, _dblp)
+BNB_LEAF_ROUTING = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, _i64p, _i32p, _i32p,
+                                    _dblp)
 
 
 class BnbEngine(ctypes.Structure):
@@ -130,7 +147,7 @@ class PyBnbEngine:
     kept in `error` (BranchAndBound re-raises it).  A model with an rc_fixings(slot, cutoff) -> (idx, val) method
     (LPModel.rc_fixings' contract) gives the tree its optional rc_fixings call, unless rc_fixings=False."""
 
-    def __init__(self, model, F, N, per_lp=True, rc_fixings=True):
+    def __init__(self, model, F, N, per_lp=True, rc_fixings=True, leaf_eval=True):
         self.model, self.F, self.N = model, int(F), int(N)
         self.n_int, self.max_batch = int(model.n_int), int(model.max_batch)
         self.error = None
@@ -231,6 +248,30 @@ class PyBnbEngine:
                 self.error = e
                 return 0
 
+        # the fixed-placement evaluator pair (nep_bnb_set_leaf_engine) of a model with leaf_eval(z, rounds, cutoff) ->
+        # dict(lower, upper, status) and leaf_routing(k) -> (row, dst, val) (LPModel's contracts), unless leaf_eval=False
+        self.leaf_calls = 0
+        self.leaf_pair = None
+
+        def leaf_ev(_, n, z, opts, pin, lower, upper, status, pout, cpu):
+            o = opts.contents
+            r = model.leaf_eval(A(z, (n, ni)).copy(), rounds=int(o.rounds), cutoff=float(o.cutoff))
+            A(lower, (n,))[:] = r["lower"]
+            A(upper, (n,))[:] = r["upper"]
+            A(status, (n,))[:] = np.asarray(r["status"], np.int32)
+            self.leaf_calls += 1
+
+        def leaf_rt(_, k, capacity, n_entries, row, dst, val):
+            r, d, v = model.leaf_routing(int(k))
+            cnt = len(r)
+            n_entries[0] = cnt
+            if cnt and capacity >= cnt:
+                A(row, (cnt,))[:] = np.asarray(r, np.int32)
+                A(dst, (cnt,))[:] = np.asarray(d, np.int32)
+                A(val, (cnt,))[:] = np.asarray(v, np.float64)
+
+        if leaf_eval and hasattr(model, "leaf_eval") and hasattr(model, "leaf_routing"):
+            self.leaf_pair = (BNB_LEAF_EVAL(guard(leaf_ev)), BNB_LEAF_ROUTING(guard(leaf_rt)))
         self.table = BnbEngine(None, ni, mb, BNB_SUBMIT(guard(submit)), BNB_ADVANCE(guard(advance)),
                                BNB_ACTIVE(active), BNB_COPY(guard(copy_state)), BNB_PARAMS(guard(set_params)),
                                BNB_FLOWS(guard(flows)), BNB_SOLS(guard(sols)), BNB_DIAG(guard(diag)),
@@ -254,7 +295,8 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_bnb_run", "nep_bnb_get_stats", "nep_bnb_get_lp_iters", "nep_bnb_incumbent", "nep_bnb_set_step2",
            "nep_bnb_incumbent_event", "nep_bnb_debug_ibound", "nep_bnb_create_engines", "nep_bnb_sync_get",
            "nep_bnb_sync_set", "nep_bnb_export_nodes", "nep_bnb_import_nodes", "nep_lp_get_reduced_costs",
-           "nep_lp_rc_fixings", "nep_debug_block_split")
+           "nep_lp_rc_fixings", "nep_debug_block_split", "nep_leaf_eval", "nep_leaf_routing_entries",
+           "nep_debug_leaf_repair", "nep_bnb_set_leaf_engine", "nep_bnb_get_leaf_stats", "nep_bnb_incumbent_routing")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -326,6 +368,9 @@ def load_library(path=None):
     lib.nep_bnb_get_lp_iters.argtypes = [vp, pi64]
     lib.nep_bnb_incumbent.argtypes = [vp, _dp, pi32, pi32, _dp]
     lib.nep_bnb_set_step2.argtypes = [vp, i32, ctypes.c_double, _dp, i32]
+    lib.nep_bnb_set_leaf_engine.argtypes = [vp, vp, BNB_LEAF_EVAL, BNB_LEAF_ROUTING]
+    lib.nep_bnb_get_leaf_stats.argtypes = [vp, ctypes.POINTER(LeafStats)]
+    lib.nep_bnb_incumbent_routing.argtypes = [vp, i64, pi64, pi32, pi32, _dp]
     lib.nep_bnb_incumbent_event.argtypes = [vp, pi32, pi32, _dp, _dp]
     lib.nep_bnb_debug_ibound.argtypes = [ctypes.POINTER(BnbParams), i32, ctypes.c_double, _dp, i32, pi32, _dp, _dp]
     lib.nep_bnb_create_engines.argtypes = [ctypes.POINTER(BnbEngine), ctypes.POINTER(BnbEngine),
@@ -342,6 +387,10 @@ def load_library(path=None):
     lib.nep_lp_score_check.argtypes = [vp, i32, _dp]
     lib.nep_round_leaf.argtypes = [i32, i32, _dp, _dp, ctypes.POINTER(ctypes.c_float), _dp, _dp, _dp, i32,
                                    ctypes.c_double, _dp, _dp]
+    lib.nep_leaf_eval.argtypes = [vp, i32, _dp, ctypes.POINTER(LeafOpts), _dp, _dp, _dp, pi32, _dp, _dp]
+    lib.nep_leaf_routing_entries.argtypes = [vp, i32, i64, pi64, pi32, pi32, _dp]
+    lib.nep_debug_leaf_repair.argtypes = [ctypes.POINTER(ModelDesc), _dp, pi32, _dp, pi32, i64, pi64, pi32, pi32, _dp,
+                                          _dp]
     lib.nep_last_error.restype = ctypes.c_char_p
     lib.nep_api_version.restype = ctypes.c_int
     # array arguments travel as plain addresses (_ptr: the array's data pointer as an int): ctypes' typed
@@ -480,6 +529,32 @@ def debug_build(data, variant, step=STEP1, alpha=0.5, soften_step1_sol=1.3, max_
            "nep_debug_build")
     return {"eta": float(eta[0]), "rho": rho, "gam": gam, "rownorm": rn, "R": R, "T": T, "n_int": n_int,
             "n_dual": n_dual}
+
+
+def debug_leaf_repair(data, variant, z, asg, alpha=0.5):
+    """Host-only (no GPU needed): the fixed-placement evaluator's repair (nep_debug_leaf_repair) of the step-1
+    placement z [n_int] from the assignment asg [R] (a destination per loaded routing row).  Returns (found, upper,
+    (row, dst, val), cpu [N])."""
+    lib = load_library()
+    N, F = len(data.nodes), len(data.functions)
+    v = VARIANTS[variant] if isinstance(variant, str) else int(variant)
+    k = _arrays(data, N, F)
+    d = _desc(k, N, F, v, STEP1, alpha, 1.3, 0.0, 0.0, data.node_budget)
+    z = np.ascontiguousarray(z, np.float64)
+    asg = np.ascontiguousarray(asg, np.int32)
+    upper, found, cnt = np.zeros(1), np.zeros(1, np.int32), np.zeros(1, np.int64)
+    cpu = np.zeros(N)
+    _check(lib, lib.nep_debug_leaf_repair(ctypes.byref(d), _ptr(z), _ptr(asg, ctypes.c_int32), _ptr(upper),
+                                          _ptr(found, ctypes.c_int32), 0, _ptr(cnt, ctypes.c_int64), None, None, None,
+                                          _ptr(cpu)), "nep_debug_leaf_repair")
+    n = int(cnt[0])
+    row, dst, val = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n)
+    if n:
+        _check(lib, lib.nep_debug_leaf_repair(ctypes.byref(d), _ptr(z), _ptr(asg, ctypes.c_int32), _ptr(upper),
+                                              _ptr(found, ctypes.c_int32), n, _ptr(cnt, ctypes.c_int64),
+                                              _ptr(row, ctypes.c_int32), _ptr(dst, ctypes.c_int32), _ptr(val),
+                                              _ptr(cpu)), "nep_debug_leaf_repair")
+    return bool(found[0]), float(upper[0]), (row, dst, val), cpu
 
 
 def debug_block_split(n_nodes, n_functions, na, relaxation=RELAX_REFERENCE):
@@ -667,6 +742,36 @@ class LPModel:
             _check(self._lib, self._lib.nep_lp_rc_fixings(self._h, int(slot), float(cutoff), k, ctypes.byref(n),
                                                           _ptr(idx, ctypes.c_int32), _ptr(val)), "nep_lp_rc_fixings")
         return idx, val
+
+    def leaf_eval(self, z, rounds=32, cutoff=math.inf, prices=None, tol=0.0):
+        """The fixed-placement evaluator (nep_leaf_eval) on placements z [n, n_int] (every c and n 0 or 1) of a
+        step-1 reference model: dict of lower [n] (Lagrangian bound on the leaf LP, best of rounds 0 .. rounds),
+        upper [n] (objective of a repaired feasible routing, inf: none), status [n] (LEAF_*), prices [n, N] (behind
+        lower) and cpu [n, N] (loads of the returned routing).  prices [n, N] >= 0: the round-0 prices."""
+        z = np.ascontiguousarray(np.asarray(z, np.float64).reshape(-1, self.n_int))
+        n = len(z)
+        pin = None if prices is None else np.ascontiguousarray(np.asarray(prices, np.float64).reshape(n, self.N))
+        lower, upper, status = np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
+        pout, cpu = np.zeros((n, self.N)), np.zeros((n, self.N))
+        opts = LeafOpts(int(rounds), float(cutoff), float(tol))
+        _check(self._lib, self._lib.nep_leaf_eval(self._h, n, _ptr(z), ctypes.byref(opts), _ptr(pin), _ptr(lower),
+                                                  _ptr(upper), _ptr(status, ctypes.c_int32), _ptr(pout), _ptr(cpu)),
+               "nep_leaf_eval")
+        return {"lower": lower, "upper": upper, "status": status, "prices": pout, "cpu": cpu}
+
+    def leaf_routing(self, k):
+        """(row, dst, val) of the routing behind upper[k] of the last leaf_eval call (nep_leaf_routing_entries;
+        routing_from_entries makes a SparseRouting of it)."""
+        n = ctypes.c_int64(0)
+        _check(self._lib, self._lib.nep_leaf_routing_entries(self._h, int(k), 0, ctypes.byref(n), None, None, None),
+               "nep_leaf_routing_entries")
+        cnt = n.value
+        row, dst, val = np.zeros(cnt, np.int32), np.zeros(cnt, np.int32), np.zeros(cnt)
+        if cnt:
+            _check(self._lib, self._lib.nep_leaf_routing_entries(self._h, int(k), cnt, ctypes.byref(n),
+                                                                 _ptr(row, ctypes.c_int32), _ptr(dst, ctypes.c_int32),
+                                                                 _ptr(val)), "nep_leaf_routing_entries")
+        return row, dst, val
 
     def rows(self, slot):
         R = self.info.n_rows

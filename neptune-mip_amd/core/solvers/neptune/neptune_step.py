@@ -92,6 +92,10 @@ class NeptuneStepBase(Solver):
     # MinDelayAndUtilization); leaves stay on the reference model
     strengthen = True
 
+    # the native tree's use of the fixed-placement evaluator (core/engine/bnb.py leaf_eval): off until
+    # its product runs are weighed
+    leaf_eval = False
+
     # bound-model slots beyond the `batch` in flight and its root's: finished branching nodes' states stay there
     # (least recently finished reused first) so their children warm-start from them (DESIGN.md §7 "Parked parents")
     bound_park = 0
@@ -286,7 +290,8 @@ class NeptuneStepBase(Solver):
                   objective_integral=self.objective_integral(),
                   # step 1: warm starts banded around 8 x the model's cold-start primal weight
                   warm_weight_ref=8.0 if self.step_id() == _lp.STEP1 else 0.0,
-                  step2_native=self.native_bound(), branching=self.branching)
+                  step2_native=self.native_bound(), branching=self.branching,
+                  leaf_eval=bool(self.leaf_eval) and self.step_id() == _lp.STEP1)
         kw.update(overrides)
         return BranchAndBound(model, data.workload_matrix, data.function_memory_matrix, data.node_memory_matrix, **kw)
 

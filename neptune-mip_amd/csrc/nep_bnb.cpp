@@ -37,6 +37,7 @@
 namespace nep {
 int set_error(int code, const char *msg);   // nep_host.cpp: nep_last_error's thread-local message
 bool model_is_facility(void *model);        // nep_host.cpp: the handle is a NEP_RELAX_FACILITY model
+bool model_has_leaf_eval(void *model);      // nep_host.cpp: the handle is a step-1 reference model (nep_leaf_eval)
 }
 
 namespace {
@@ -78,6 +79,7 @@ struct Node {
   double bfrac = 0.0, pbound = -std::numeric_limits<double>::infinity();
   std::shared_ptr<SbWait> sb;   // STRONG: the branching node its probe belongs to, candidate sb_i
   int sb_i = -1;
+  bool evald = false;           // the fixed-placement evaluator has seen this leaf (p.leaf_eval)
 };
 using NodeP = std::shared_ptr<Node>;
 
@@ -224,6 +226,14 @@ struct NepBnb {
   int keep_slot = -1;        // (warm = 0) a working slot kept for the incumbent
   NodeP inc_node;
   std::vector<double> inc_z;
+  // fixed-placement evaluator (p.leaf_eval): the leaf engine's pair, the evaluator incumbent's entries
+  void *le_ctx = nullptr;
+  nep_bnb_leaf_eval_fn le_eval = nullptr;
+  nep_bnb_leaf_routing_fn le_routing = nullptr;
+  nep_bnb_leaf_stats lst{};
+  std::vector<int32_t> inc_row, inc_dst;
+  std::vector<double> inc_val;
+  int eval_leaves();
   nep_bnb_stats st{};
   double t0 = 0.0;
   bool started = false, finished = false, limit_hit = false;
@@ -345,6 +355,85 @@ bool ops_complete(const nep_bnb_engine &o) {
 
 // one submit per (engine, warm, check_every) group — and per (budget, bound_res) too when the engine has no
 // submit_ex (per-LP budgets) — warm-start copies first
+// The queued leaves and retries that fix every c and n and the evaluator has not seen, in one call at the current
+// cutoff (include/neptune_lp.h "The tree's use of the fixed-placement evaluator").
+int NepBnb::eval_leaves() {
+  std::vector<NodeP> batch;
+  for (std::deque<NodeP> *q : {&retry, &pending})
+    for (const NodeP &c : *q)
+      if (!c->evald && (c->kind == LEAF || c->kind == RETRY) && (int)c->idx.size() >= nb()) batch.push_back(c);
+  if (batch.empty()) return NEP_OK;
+  const double t_in = now_s();
+  const size_t ni = (size_t)L.n_int, nn = batch.size();
+  std::vector<double> z(nn * ni, 0.0), lower(nn), upper(nn);
+  std::vector<int32_t> status(nn);
+  for (size_t b = 0; b < nn; ++b) {
+    const Node &n = *batch[b];
+    batch[b]->evald = true;
+    for (size_t k = 0; k < n.idx.size(); ++k) z[b * ni + (size_t)n.idx[k]] = n.val[k];
+  }
+  nep_leaf_opts o{};
+  o.rounds = p.leaf_rounds > 0 ? p.leaf_rounds : 32;
+  o.cutoff = std::min(incv() - gap_abs(incv()), p.upper_bound);
+  o.tol = 0.0;
+  int rc = le_eval(le_ctx, (int32_t)nn, z.data(), &o, nullptr, lower.data(), upper.data(), status.data(), nullptr,
+                   nullptr);
+  if (rc) return rc;
+  lst.leaf_eval_calls += 1;
+  lst.leaf_eval_leaves += (int64_t)nn;
+  std::vector<char> drop(nn, 0);
+  for (size_t b = 0; b < nn; ++b) {
+    Node &n = *batch[b];
+    if (status[b] == NEP_LEAF_INFEASIBLE || status[b] == NEP_LEAF_CUTOFF) {
+      drop[b] = 1;
+      lst.leaf_eval_dropped += 1;
+      continue;
+    }
+    if (upper[b] < INF && upper[b] < incv() - gap_abs(incv()) && upper[b] <= p.upper_bound) {
+      int64_t cnt = 0;
+      rc = le_routing(le_ctx, (int32_t)b, 0, &cnt, nullptr, nullptr, nullptr);
+      if (rc) return rc;
+      inc_row.assign((size_t)cnt, 0);
+      inc_dst.assign((size_t)cnt, 0);
+      inc_val.assign((size_t)cnt, 0.0);
+      rc = le_routing(le_ctx, (int32_t)b, cnt, &cnt, inc_row.data(), inc_dst.data(), inc_val.data());
+      if (rc) return rc;
+      inc = upper[b];
+      inc_source = 3;
+      inc_node = batch[b];
+      inc_z.assign(z.begin() + b * ni, z.begin() + (b + 1) * ni);
+      inc_slot = -1;
+      if (keep_slot >= 0) {   // (warm = 0: the slot kept for an LP incumbent's state)
+        L.free.push_back(keep_slot);
+        keep_slot = -1;
+      }
+      lst.leaf_eval_incumbents += 1;
+      rc = set_cutoffs();
+      if (rc) return rc;
+    }
+    if (status[b] == NEP_LEAF_EXACT) {   // the leaf's LP value is upper (within the evaluator's tolerance): resolved
+      drop[b] = 1;
+      lst.leaf_eval_exact += 1;
+      continue;
+    }
+    if (status[b] == NEP_LEAF_FEASIBLE) lst.leaf_eval_feasible += 1;
+    n.bound = std::max(n.bound, lower[b]);
+  }
+  // (a leaf whose raised bound reaches the cutoff — the last incumbent's — is dropped too; the rest keep their place)
+  for (size_t b = 0; b < nn; ++b)
+    if (!drop[b] && pruned(batch[b]->bound)) {
+      drop[b] = 1;
+      lst.leaf_eval_dropped += 1;
+    }
+  std::unordered_set<const Node *> gone;
+  for (size_t b = 0; b < nn; ++b)
+    if (drop[b]) gone.insert(batch[b].get());
+  for (std::deque<NodeP> *q : {&retry, &pending})
+    q->erase(std::remove_if(q->begin(), q->end(), [&](const NodeP &n) { return gone.count(n.get()) != 0; }), q->end());
+  lst.leaf_eval_seconds += now_s() - t_in;
+  return NEP_OK;
+}
+
 int NepBnb::submit(std::vector<std::pair<Engine *, std::pair<int, NodeP>>> &items) {
   struct Group {
     Engine *eng;
@@ -1329,7 +1418,10 @@ void *nep_bnb_create(void *leaf_model, void *bound_model, const nep_bnb_params *
   nep_bnb_engine le{}, be{};
   if (model_ops(leaf_model, &le)) return nullptr;   // (nep_model_get_info set the message)
   if (bound_model && model_ops(bound_model, &be)) return nullptr;
-  return nep_bnb_create_engines(&le, bound_model ? &be : nullptr, params, fn_mem, node_mem);
+  void *tree = nep_bnb_create_engines(&le, bound_model ? &be : nullptr, params, fn_mem, node_mem);
+  if (tree && nep::model_has_leaf_eval(leaf_model))
+    nep_bnb_set_leaf_engine(tree, leaf_model, nep_leaf_eval, nep_leaf_routing_entries);
+  return tree;
 }
 
 void nep_bnb_destroy(void *tree) { delete static_cast<NepBnb *>(tree); }
@@ -1489,6 +1581,10 @@ int nep_bnb_run(void *tree, int32_t *event) {
       T.limit_hit = true;
       break;
     }
+    if (T.p.leaf_eval && T.le_eval && !sharded && L.root_ready) {   // queued leaves through the evaluator first
+      const int rc = T.eval_leaves();
+      if (rc) return rc;
+    }
     // fill the free slots: retries, rounding leaves, then best-first open nodes
     std::vector<std::pair<Engine *, std::pair<int, NodeP>>> items;
     // at most `batch` LPs in flight per model; further free slots keep finished states (parked parents)
@@ -1606,6 +1702,43 @@ int nep_bnb_run(void *tree, int32_t *event) {
   return NEP_OK;
 }
 
+int nep_bnb_set_leaf_engine(void *tree, void *ctx, nep_bnb_leaf_eval_fn leaf_eval,
+                            nep_bnb_leaf_routing_fn leaf_routing_entries) {
+  auto *t = static_cast<NepBnb *>(tree);
+  if (!t) return bad(NEP_ERR_ARG, "nep_bnb_set_leaf_engine: null tree");
+  if (t->started) return bad(NEP_ERR_STATE, "nep_bnb_set_leaf_engine: the search has started");
+  const bool both = leaf_eval && leaf_routing_entries;
+  t->le_ctx = both ? ctx : nullptr;
+  t->le_eval = both ? leaf_eval : nullptr;
+  t->le_routing = both ? leaf_routing_entries : nullptr;
+  return NEP_OK;
+}
+
+int nep_bnb_get_leaf_stats(void *tree, nep_bnb_leaf_stats *out) {
+  auto *t = static_cast<NepBnb *>(tree);
+  if (!t || !out) return bad(NEP_ERR_ARG, "nep_bnb_get_leaf_stats: null argument");
+  *out = t->lst;
+  return NEP_OK;
+}
+
+int nep_bnb_incumbent_routing(void *tree, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst,
+                              double *val) {
+  auto *t = static_cast<NepBnb *>(tree);
+  if (!t || !n_entries) return bad(NEP_ERR_ARG, "nep_bnb_incumbent_routing: null argument");
+  if (t->inc_source != 3) {
+    *n_entries = -1;
+    return NEP_OK;
+  }
+  const int64_t cnt = (int64_t)t->inc_row.size();
+  *n_entries = cnt;
+  if (capacity < cnt) return NEP_OK;
+  if (!row || !dst || !val) return bad(NEP_ERR_ARG, "nep_bnb_incumbent_routing: null argument");
+  std::memcpy(row, t->inc_row.data(), cnt * sizeof(int32_t));
+  std::memcpy(dst, t->inc_dst.data(), cnt * sizeof(int32_t));
+  std::memcpy(val, t->inc_val.data(), cnt * sizeof(double));
+  return NEP_OK;
+}
+
 int nep_bnb_sync_get(void *tree, double *out6) {
   auto *t = static_cast<NepBnb *>(tree);
   if (!t || !out6) return bad(NEP_ERR_ARG, "nep_bnb_sync_get: null argument");
@@ -1678,7 +1811,7 @@ int nep_bnb_get_lp_iters(void *tree, int64_t *out) {
 int nep_bnb_incumbent(void *tree, double *z, int32_t *n_fix, int32_t *idx, double *val) {
   auto *t = static_cast<NepBnb *>(tree);
   if (!t) return bad(NEP_ERR_ARG, "nep_bnb_incumbent: null tree");
-  if (t->inc_source != 1 || !t->inc_node) {
+  if ((t->inc_source != 1 && t->inc_source != 3) || !t->inc_node) {
     if (n_fix) *n_fix = -1;
     return NEP_OK;
   }

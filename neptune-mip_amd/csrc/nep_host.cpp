@@ -22,8 +22,10 @@
 
 #include "../../include/neptune_lp.h"
 #include "nep_internal.h"
+#include "nep_leaf.h"
 
 namespace nep {
+hipError_t launch_leaf_rounds(const LeafView &v, int rounds, int threads, hipStream_t s);
 hipError_t launch_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
                          bool plain, int it, hipStream_t s, int policy_slots = 0);
 int block_tile_waves(const DeviceView &v, int nslots, bool check);
@@ -225,6 +227,21 @@ struct Model {
   double *d_rcval = nullptr;
   // per slot: the LP submitted last was refused by presolve, so the slot's kept reduced costs are an earlier LP's
   std::vector<uint8_t> rc_stale;
+  // fixed-placement evaluator (nep_leaf_eval; step-1 reference models): the objective's routing scale, the instance's
+  // fp64 delay matrix on the host (Dh; W / cprh / capn hold the rest), and — from the first call on — the
+  // device workspace of one chunk of placements, its pinned staging and the last call's points
+  double kobj = 0.0;
+  struct LeafWork {
+    int cap = 0, threads = 64;
+    LeafView v{};
+    void *pinned = nullptr;
+    uint8_t *h_open = nullptr;
+    LeafCtrl *h_ctrl = nullptr;
+    double *h_y = nullptr, *h_load = nullptr;
+    int32_t *h_asg0 = nullptr;
+    std::vector<LeafPoint> points;
+  };
+  std::unique_ptr<LeafWork> leaf;
   // pinned staging of nep_lp_submit's uploads (slots, change offsets / indices / bounds, exact flags): the
   // call returns without waiting for them; two stagings alternate, and a submit waits on the event of the
   // one it rewrites (recorded after that staging's copies, two submits earlier: normally long done)
@@ -243,6 +260,7 @@ struct Model {
     if (h_flows) (void)hipHostFree(h_flows);
     if (h_sols) (void)hipHostFree(h_sols);
     if (h_rc) (void)hipHostFree(h_rc);
+    if (leaf && leaf->pinned) (void)hipHostFree(leaf->pinned);
     for (int k = 0; k < 2; ++k) {
       if (h_sub_i[k]) (void)hipHostFree(h_sub_i[k]);
       if (h_sub_d[k]) (void)hipHostFree(h_sub_d[k]);
@@ -376,6 +394,7 @@ int build(Model &m, const nep_model_desc &d, bool host_power = true) {
     }
     m.cost_n = d.variant == NEP_MIN_UTILIZATION ? 1.0 : d.variant == NEP_MIN_DELAY_AND_UTILIZATION ? d.alpha / N : 0.0;
   }
+  m.kobj = kobj;
   double score_rhs = INF;
   std::vector<double> colmaxD(N, -INF);
   for (int k = 0; k < N; ++k)
@@ -397,7 +416,8 @@ int build(Model &m, const nep_model_desc &d, bool host_power = true) {
     m.row_wsc_d[r] = wsc;
     if (wsc != 0.0) m.score_x = true;
   }
-  if (m.score_x) m.Dh.assign(D, D + (size_t)N * N);
+  // (step-1 reference models keep it too: the fixed-placement evaluator's fp64 delays, nep_leaf_eval)
+  if (m.score_x || (!m.step2 && !m.fac)) m.Dh.assign(D, D + (size_t)N * N);
   if (m.step2) {
     if (d.variant == NEP_MIN_DELAY) {
       score_rhs = d.soften_step1_sol * d.prev_network_delay;
@@ -1992,6 +2012,10 @@ int score_check(Model &m, int slot, double *out) {
 namespace nep {
 // (nep_bnb.cpp: nep_bnb_create gives the tree nep_lp_rc_fixings only for a facility-relaxation model)
 bool model_is_facility(void *model) { return model && static_cast<Model *>(model)->fac != 0; }
+// (nep_bnb.cpp: nep_bnb_create gives the tree the fixed-placement evaluator only for a step-1 reference model)
+bool model_has_leaf_eval(void *model) {
+  return model && !static_cast<Model *>(model)->fac && !static_cast<Model *>(model)->step2;
+}
 }
 
 // =============================================================================================
@@ -2599,6 +2623,256 @@ int nep_get_stats(void *model, nep_stats *stats) {
 
 void nep_reset_stats(void *model) {
   if (model) static_cast<Model *>(model)->stats = nep_stats{};
+}
+
+// ---------------------------------------------------------------------------------------------
+// fixed-placement evaluator (nep_leaf.hip, nep_leaf_repair.cpp)
+// ---------------------------------------------------------------------------------------------
+static const char *const kLeafRefusal =
+    "the fixed-placement evaluator takes step-1 reference-relaxation models (NEP_STEP1, NEP_RELAX_REFERENCE)";
+
+static LeafInstance leaf_instance(const Model &m) {
+  LeafInstance in{};
+  in.N = m.N; in.F = m.F; in.R = m.R; in.has_n = m.has_n;
+  in.eps = m.eps; in.kobj = m.kobj; in.cost_n = m.cost_n;
+  in.D = m.Dh.data(); in.W = m.W.data(); in.cpr = m.cprh.data(); in.cores = m.capn.data() + m.N;
+  in.row_f = m.row_f.data(); in.row_src = m.row_src.data(); in.frow = m.frow.data();
+  return in;
+}
+
+// every c and n of z is 0 or 1; c_open [F*N] gets c, *nsum the open nodes
+static bool leaf_binary(const Model &m, const double *z, uint8_t *c_open, double *nsum) {
+  const int FN = m.F * m.N;
+  for (int k = 0; k < m.il.n_int; ++k)
+    if (z[k] != 0.0 && z[k] != 1.0) return false;
+  for (int k = 0; k < FN; ++k) c_open[k] = z[m.il.oc + k] != 0.0;
+  double s = 0.0;
+  for (int j = 0; j < m.N && m.has_n; ++j) s += z[m.il.on + j];
+  *nsum = s;
+  return true;
+}
+
+// a row without x rejects the placement: C3 memory, C6/C7 n against c, C8 budget, a function without a destination
+static bool leaf_rejects(const Model &m, const double *z, const uint8_t *c_open) {
+  const int N = m.N, F = m.F;
+  for (int j = 0; j < N; ++j) {
+    double mem = 0.0;
+    bool any = false;
+    for (int f = 0; f < F; ++f)
+      if (c_open[(size_t)f * N + j]) { mem += m.mem_f[f]; any = true; }
+    if (mem > m.capn[j] + 1e-9) return true;
+    if (m.has_n) {
+      const double nj = z[m.il.on + j];
+      if (any != (nj != 0.0)) return true;
+      if (m.node_cost[j] * nj > m.node_budget + 1e-9) return true;
+    }
+  }
+  for (int f = 0; f < F; ++f) {
+    bool any = false;
+    for (int j = 0; j < N && !any; ++j) any = c_open[(size_t)f * N + j] != 0;
+    if (!any) return true;
+  }
+  return false;
+}
+
+// the evaluator's workspace, on first use: one chunk of `cap` placements (the shares, [cap][F][N] doubles, held to
+// 64 MiB; at most 64 placements), the fp64 instance on the device and the pinned staging of a chunk
+static int ensure_leaf_alloc(Model &m);
+static int ensure_leaf(Model &m) {
+  if (m.leaf) return NEP_OK;
+  // a failure part-way gives back what this call allocated (the next call starts over)
+  const size_t n0 = m.allocs.size();
+  const int rc = ensure_leaf_alloc(m);
+  if (rc) {
+    while (m.allocs.size() > n0) {
+      (void)hipFree(m.allocs.back());
+      m.allocs.pop_back();
+    }
+  }
+  return rc;
+}
+static int ensure_leaf_alloc(Model &m) {
+  std::unique_ptr<Model::LeafWork> w(new Model::LeafWork());
+  const size_t N = m.N, F = m.F, R = m.R;
+  w->cap = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)64 << 20) / (F * N * sizeof(double))));
+  int maxrf = 1;
+  for (int f = 0; f < m.F; ++f) maxrf = std::max(maxrf, m.frow[f + 1] - m.frow[f]);
+  // leaf_assign's workgroup: sized to the rows of a function while every function takes them a lane per row (N <=
+  // kLeafLaneK: no open list is longer); else a function may take a wave per row, and gets all four waves
+  w->threads = m.N > kLeafLaneK ? kLeafThreads : maxrf <= 64 ? 64 : maxrf <= 128 ? 128 : kLeafThreads;
+  const size_t B = w->cap;
+  LeafView &v = w->v;
+  v.N = m.N; v.F = m.F; v.R = m.R; v.B = 0; v.kobj = m.kobj;
+  v.frow = m.v.frow;
+  int rc;
+  std::vector<int32_t> src(m.row_src.begin(), m.row_src.end());
+  std::vector<double> cores(m.capn.begin() + N, m.capn.end());
+  if ((rc = upload(m, &v.row_src, src))) return rc;
+  if ((rc = upload(m, &v.D, m.Dh))) return rc;
+  if ((rc = upload(m, &v.W, m.W))) return rc;
+  if ((rc = upload(m, &v.cpr, m.cprh))) return rc;
+  if ((rc = upload(m, &v.cores, cores))) return rc;
+  uint8_t *d_open = nullptr;
+  if ((rc = dalloc(m, &d_open, B * F * N))) return rc;
+  v.open = d_open;
+  if ((rc = dalloc(m, &v.y, B * N))) return rc;
+  if ((rc = dalloc(m, &v.ybest, B * N))) return rc;
+  if ((rc = dalloc(m, &v.share, B * F * N))) return rc;
+  if ((rc = dalloc(m, &v.fpart, B * F))) return rc;
+  if ((rc = dalloc(m, &v.load, B * N))) return rc;
+  if ((rc = dalloc(m, &v.g, B * N))) return rc;
+  if ((rc = dalloc(m, &v.asg0, B * R))) return rc;
+  if ((rc = dalloc(m, &v.asg, B * R))) return rc;
+  if ((rc = dalloc(m, &v.ctrl, B))) return rc;
+  // pinned: [ctrl | y | load | asg0 | open]
+  const size_t bytes = B * (sizeof(LeafCtrl) + 2 * N * sizeof(double) + R * sizeof(int32_t) + F * N) + 64;
+  if (hipHostMalloc(&w->pinned, bytes) != hipSuccess) return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator)");
+  char *p = static_cast<char *>(w->pinned);
+  w->h_ctrl = reinterpret_cast<LeafCtrl *>(p); p += B * sizeof(LeafCtrl);
+  w->h_y = reinterpret_cast<double *>(p); p += B * N * sizeof(double);
+  w->h_load = reinterpret_cast<double *>(p); p += B * N * sizeof(double);
+  w->h_asg0 = reinterpret_cast<int32_t *>(p); p += B * R * sizeof(int32_t);
+  w->h_open = reinterpret_cast<uint8_t *>(p);
+  m.leaf = std::move(w);
+  return NEP_OK;
+}
+
+int nep_leaf_eval(void *model, int32_t n, const double *z_leaf, const nep_leaf_opts *opts, const double *prices_in,
+                  double *lower, double *upper, int32_t *status, double *prices_out, double *cpu) {
+  if (!model || !z_leaf || !lower || !upper || !status) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  if (n < 1) return fail(NEP_ERR_ARG, "n must be at least 1");
+  const int rounds = opts ? opts->rounds : 32;
+  const double cutoff = opts ? opts->cutoff : INF;
+  const double tol = opts && opts->tol > 0.0 ? opts->tol : 1e-6;
+  if (rounds < 0 || cutoff != cutoff) return fail(NEP_ERR_ARG, "bad rounds or cutoff");
+  const size_t N = m.N, F = m.F, R = m.R, ni = m.il.n_int;
+  for (size_t k = 0; k < (size_t)n * ni; ++k)
+    if (z_leaf[k] != 0.0 && z_leaf[k] != 1.0)
+      return fail(NEP_ERR_ARG, "placement " + std::to_string(k / ni) + ": entry " + std::to_string(k % ni) +
+                                   " is not 0 or 1 (a leaf fixes every c and n)");
+  for (size_t k = 0; prices_in && k < (size_t)n * N; ++k)
+    if (!(prices_in[k] >= 0.0) || prices_in[k] == INF) return fail(NEP_ERR_ARG, "prices_in must be finite and >= 0");
+  int rc = ensure_leaf(m);
+  if (rc) return rc;
+  Model::LeafWork &w = *m.leaf;
+  w.points.assign(n, LeafPoint());
+  const LeafInstance in = leaf_instance(m);
+  std::vector<uint8_t> c_open(F * N);
+  std::vector<int> todo;   // the placements that reach the device
+  for (int b = 0; b < n; ++b) {
+    double nsum = 0.0;
+    leaf_binary(m, z_leaf + b * ni, c_open.data(), &nsum);
+    if (prices_out) std::fill(prices_out + b * N, prices_out + (b + 1) * N, 0.0);
+    if (cpu) std::fill(cpu + b * N, cpu + (b + 1) * N, 0.0);
+    if (leaf_rejects(m, z_leaf + b * ni, c_open.data())) {
+      lower[b] = upper[b] = INF;
+      status[b] = NEP_LEAF_INFEASIBLE;
+    } else {
+      todo.push_back(b);
+    }
+  }
+  for (size_t t0 = 0; t0 < todo.size(); t0 += w.cap) {
+    const int B = (int)std::min<size_t>(w.cap, todo.size() - t0);
+    std::vector<double> nsums(B);
+    for (int q = 0; q < B; ++q) {
+      const int b = todo[t0 + q];
+      leaf_binary(m, z_leaf + b * ni, w.h_open + q * F * N, &nsums[q]);
+      LeafCtrl &c = w.h_ctrl[q];
+      c = LeafCtrl{};
+      c.base = m.has_n ? m.cost_n * nsums[q] : 0.0;
+      c.best = -INF;
+      c.lam = 1.0;
+      c.cutoff = cutoff;
+      if (prices_in) std::memcpy(w.h_y + q * N, prices_in + b * N, N * sizeof(double));
+      else std::fill(w.h_y + q * N, w.h_y + (q + 1) * N, 0.0);
+    }
+    LeafView v = w.v;
+    v.B = B;
+    HIPCHK(hipMemcpyAsync(const_cast<uint8_t *>(v.open), w.h_open, B * F * N, hipMemcpyHostToDevice, m.aux));
+    HIPCHK(hipMemcpyAsync(v.ctrl, w.h_ctrl, B * sizeof(LeafCtrl), hipMemcpyHostToDevice, m.aux));
+    HIPCHK(hipMemcpyAsync(v.y, w.h_y, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
+    HIPCHK(hipMemcpyAsync(v.ybest, w.h_y, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
+    HIPCHK(launch_leaf_rounds(v, rounds, w.threads, m.aux));
+    // one read at the end: bounds and flags, the best prices, the last loads, the round-0 assignment
+    HIPCHK(hipMemcpyAsync(w.h_ctrl, v.ctrl, B * sizeof(LeafCtrl), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_y, v.ybest, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_load, v.load, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_asg0, v.asg0, B * R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipStreamSynchronize(m.aux));
+    for (int q = 0; q < B; ++q) {
+      const int b = todo[t0 + q];
+      const LeafCtrl &c = w.h_ctrl[q];
+      lower[b] = c.best;
+      upper[b] = INF;
+      if (prices_out) std::memcpy(prices_out + b * N, w.h_y + q * N, N * sizeof(double));
+      if (cpu) std::memcpy(cpu + b * N, w.h_load + q * N, N * sizeof(double));
+      if (c.cut) {
+        status[b] = NEP_LEAF_CUTOFF;
+        continue;
+      }
+      LeafPoint &pt = w.points[b];
+      leaf_repair(in, w.h_open + q * F * N, nsums[q], w.h_asg0 + q * R, pt);
+      if (!pt.found) {
+        status[b] = NEP_LEAF_NO_POINT;
+        continue;
+      }
+      upper[b] = pt.obj;
+      if (cpu) std::memcpy(cpu + b * N, pt.cpu.data(), N * sizeof(double));
+      status[b] = pt.obj - c.best <= tol * std::max(1.0, std::fabs(c.best)) ? NEP_LEAF_EXACT : NEP_LEAF_FEASIBLE;
+    }
+  }
+  return NEP_OK;
+}
+
+int nep_leaf_routing_entries(void *model, int32_t k, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst,
+                             double *val) {
+  if (!model || !n_entries) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  if (!m.leaf || k < 0 || (size_t)k >= m.leaf->points.size())
+    return fail(NEP_ERR_ARG, "no placement " + std::to_string(k) + " in the last nep_leaf_eval call");
+  const LeafPoint &pt = m.leaf->points[k];
+  if (!pt.found) return fail(NEP_ERR_STATE, "placement " + std::to_string(k) + " has no routing (upper = +inf)");
+  const int64_t cnt = (int64_t)pt.row.size();
+  *n_entries = cnt;
+  if (capacity < cnt) return NEP_OK;   // size query
+  if (!row || !dst || !val) return fail(NEP_ERR_ARG, "null argument");
+  std::memcpy(row, pt.row.data(), cnt * sizeof(int32_t));
+  std::memcpy(dst, pt.dst.data(), cnt * sizeof(int32_t));
+  std::memcpy(val, pt.val.data(), cnt * sizeof(double));
+  return NEP_OK;
+}
+
+int nep_debug_leaf_repair(const nep_model_desc *desc, const double *z_leaf, const int32_t *asg, double *upper,
+                          int32_t *found, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst, double *val,
+                          double *cpu) {
+  if (!desc || !z_leaf || !asg || !upper || !found || !n_entries) return fail(NEP_ERR_ARG, "null argument");
+  if (desc->device_inputs) return fail(NEP_ERR_ARG, "nep_debug_leaf_repair takes host arrays (device_inputs = 0)");
+  Model m;
+  int rc = build(m, *desc);
+  if (rc) return rc;
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  std::vector<uint8_t> c_open((size_t)m.F * m.N);
+  double nsum = 0.0;
+  if (!leaf_binary(m, z_leaf, c_open.data(), &nsum)) return fail(NEP_ERR_ARG, "a leaf fixes every c and n at 0 or 1");
+  LeafPoint pt;
+  *found = 0;
+  *upper = INF;
+  *n_entries = 0;
+  if (leaf_rejects(m, z_leaf, c_open.data())) return NEP_OK;
+  leaf_repair(leaf_instance(m), c_open.data(), nsum, asg, pt);
+  if (cpu && !pt.cpu.empty()) std::memcpy(cpu, pt.cpu.data(), m.N * sizeof(double));
+  if (!pt.found) return NEP_OK;
+  *found = 1;
+  *upper = pt.obj;
+  *n_entries = (int64_t)pt.row.size();
+  if (capacity < *n_entries || !row || !dst || !val) return NEP_OK;
+  std::memcpy(row, pt.row.data(), pt.row.size() * sizeof(int32_t));
+  std::memcpy(dst, pt.dst.data(), pt.dst.size() * sizeof(int32_t));
+  std::memcpy(val, pt.val.data(), pt.val.size() * sizeof(double));
+  return NEP_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,68 @@
+// nep_leaf.h — the fixed-placement evaluator (nep_leaf_eval; DESIGN.md §7 "Fixed-placement evaluator"):
+// what its device rounds (nep_leaf.hip), its host repair (nep_leaf_repair.cpp) and the ABI (nep_host.cpp) share.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+namespace nep {
+
+// The step rule of the price rounds (leaf_step, nep_leaf.hip; tests/leaf_ref.py carries the same constants): a Polyak
+// step theta = lam (target - L) / |g|^2 toward the cutoff when it is finite, else toward
+// best + kLeafMargin max(|best - base|, kLeafMarginFloor max(1, |best|)), where base = cost_n sum n is constant at a leaf
+// (the margin scales with the routing part of the bound; measured on the fixture's congested leaves against a margin
+// on |best|: the same bound after 64 rounds, a faster start where the node costs dominate); lam starts at 1 and halves
+// after kLeafStall rounds in a row that did not raise the best bound.
+constexpr double kLeafMargin = 0.05;
+constexpr double kLeafMarginFloor = 1e-3;
+constexpr int kLeafStall = 4;
+// rows of a function are taken a lane per row while it has at most this many open destinations, else a wave per row
+constexpr int kLeafLaneK = 16;
+constexpr int kLeafThreads = 256;
+
+// per-placement state of the rounds (device, one per placement of a chunk)
+struct LeafCtrl {
+  double base;      // cost_n sum n
+  double best;      // best Lagrangian value so far (-inf before round 0)
+  double lam;       // step scale
+  double cutoff;
+  int32_t stall;    // rounds in a row without a better bound
+  int32_t done;     // 1: the placement's rounds have stopped (cut off, or a zero subgradient)
+  int32_t cut;      // best >= cutoff
+  int32_t pad_;
+};
+
+// device arrays of one chunk of placements
+struct LeafView {
+  int N, F, R, B;
+  double kobj;
+  const int32_t *frow, *row_src;   // [F + 1], [R]
+  const double *D, *W, *cpr, *cores;   // fp64 instance: [N][N], [F][N], [F][N], [N]
+  const uint8_t *open;   // [B][F][N] the placements' c
+  double *y, *ybest;     // [B][N] prices: current, behind the best bound
+  double *share;         // [B][F][N] CPU load of function f on node j
+  double *fpart;         // [B][F] the functions' summed row minima
+  double *load, *g;      // [B][N] CPU load, subgradient
+  int32_t *asg0, *asg;   // [B][R] round-0 / current assignment (-1: pooled row)
+  LeafCtrl *ctrl;        // [B]
+};
+
+// the host's fp64 view of a step-1 instance
+struct LeafInstance {
+  int N, F, R, has_n;
+  double eps, kobj, cost_n;
+  const double *D, *W, *cpr, *cores;
+  const int *row_f, *row_src, *frow;
+};
+
+struct LeafPoint {
+  bool found = false;
+  double obj = 0.0;
+  int64_t ties = 0;      // moves whose best score another candidate shared (the fixture generator asserts none)
+  std::vector<int32_t> row, dst;
+  std::vector<double> val, cpu;
+};
+
+// host repair of an assignment asg [R] (destination per loaded row) at the placement c_open [F][N] with nsum open nodes
+void leaf_repair(const LeafInstance &in, const uint8_t *c_open, double nsum, const int32_t *asg, LeafPoint &out);
+
+}  // namespace nep
