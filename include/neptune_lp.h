@@ -281,6 +281,34 @@ int nep_leaf_routing_entries(void *model, int32_t k, int64_t capacity, int64_t *
 int nep_debug_leaf_repair(const nep_model_desc *desc, const double *z_leaf, const int32_t *asg, double *upper,
                           int32_t *found, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst, double *val,
                           double *cpu);
+/* nep_debug_leaf_repair from given CPU loads load [N] of asg (NULL: summed from asg in row order, which is
+ * nep_debug_leaf_repair), as nep_leaf_eval_ex repairs the round the device chose from that round's loads. */
+int nep_debug_leaf_repair_from(const nep_model_desc *desc, const double *z_leaf, const int32_t *asg, const double *load,
+                               double *upper, int32_t *found, int64_t capacity, int64_t *n_entries, int32_t *row,
+                               int32_t *dst, double *val, double *cpu);
+
+/* nep_leaf_eval with a repair of later rounds' assignments as well (csrc/nep_leaf_heur.hip).  Every price round ends in
+ * an assignment that pushes load off congested nodes; with heur->repair_every = k >= 1 the device repairs the
+ * assignments of rounds k, 2k, ... and of the last round by the host repair's rules (one workgroup per placement, at
+ * most kLeafDevMoves moves a round, no entries), keeps per placement the cheapest round (the earliest on ties) with its
+ * assignment and loads, and the host runs its fp64-verified repair on that round's assignment as well as on round 0's
+ * and returns the cheaper point: the device only chooses the round, every returned routing is the host's.
+ * heur NULL or repair_every = 0: nep_leaf_eval's results bit for bit (and no further allocation or launch).
+ *   upper_round [n]   the round behind upper[b]: 0 the round-0 repair, -1 no point
+ *   device_upper [n]  the device's own best objective (+inf: none); a verdict the host does not confirm costs a
+ *                     candidate, never correctness
+ *   round_upper [n][rounds + 1] (or NULL) the device's objective per round, +inf where the round was not repaired or
+ *                     ended without a point (for tests and probes)
+ * lower, prices_out and the statuses' meaning are nep_leaf_eval's; status, cpu and nep_leaf_routing_entries follow the
+ * returned point.  Placements that are cut off or whose prices became optimal stop their repairs with their rounds. */
+typedef struct {
+  int32_t repair_every;        /* 0: off */
+  int32_t reserved;
+} nep_leaf_heur_opts;
+int nep_leaf_eval_ex(void *model, int32_t n, const double *z_leaf /* [n][n_int] */, const nep_leaf_opts *opts,
+                     const nep_leaf_heur_opts *heur, const double *prices_in, double *lower, double *upper,
+                     int32_t *status, double *prices_out, double *cpu, int32_t *upper_round /* [n] or NULL */,
+                     double *device_upper /* [n] or NULL */, double *round_upper /* [n][rounds + 1] or NULL */);
 
 /* The reference's offline scorers and feasibility checkers on a slot's solution, on the device
  * (efttc/utils/objectives.py:23-98, efttc/utils/constraints_step1.py:5-133; booleans are the
@@ -386,7 +414,9 @@ typedef struct {
                                       for MinDelayAndUtilization without workload, whose objective is alpha / N sum n */
   int32_t leaf_eval;               /* 1 = queued leaves and retries go through the fixed-placement evaluator in one call
                                       before their LPs are submitted (needs the leaf engine's evaluator pair, see
-                                      nep_bnb_set_leaf_engine; single rank only); 0 (default): off */
+                                      nep_bnb_set_leaf_engine; single rank only); 2 = the same, and nep_bnb_create installs
+                                      the evaluator with every round's assignment repaired on the device
+                                      (nep_leaf_eval_ex, repair_every = 1); 0 (default): off */
   int32_t leaf_rounds;             /* the evaluator's price rounds per call (<= 0: 32) */
 } nep_bnb_params;
 

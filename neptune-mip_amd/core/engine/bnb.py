@@ -240,8 +240,9 @@ class BranchAndBound:
         self._rc_warned = False
         # fixed-placement evaluator (native tree; DESIGN.md §7 "Fixed-placement evaluator"): queued leaves go through
         # the leaf model's leaf_eval in one call before their LPs are submitted — dropped, resolved, made the
-        # incumbent (BnBResult.incumbent_source 3) or given a better bound.  Off by default.
-        self.leaf_eval = bool(leaf_eval)
+        # incumbent (BnBResult.incumbent_source 3) or given a better bound.  2: with every round's assignment repaired on
+        # the device as well (nep_leaf_eval_ex, repair_every = 1).  Off by default.
+        self.leaf_eval = int(leaf_eval)
         self.leaf_rounds = int(leaf_rounds)
         self._leaf_warned = False
         # (the leaf / reference model only — the model whose node LPs the replay measured; the facility relaxation
@@ -856,7 +857,7 @@ class BranchAndBound:
                       world=int(comm.world), rank=int(comm.rank), branching=self.branching,
                       strong_cands=self.strong_cands, strong_rel=self.strong_rel, strong_iters=self.strong_iters,
                       rc_fixing=1 if self.rc_fixing else 0, objective_unit=float(self.objective_unit),
-                      leaf_eval=1 if self.leaf_eval else 0, leaf_rounds=int(self.leaf_rounds))
+                      leaf_eval=int(self.leaf_eval), leaf_rounds=int(self.leaf_rounds))
         py_engines = []
         if hasattr(lp, "_h"):
             tree = lib.nep_bnb_create(lp._h, self.bound_lp._h if self.two else None, ctypes.byref(p),

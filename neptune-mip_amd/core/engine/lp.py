@@ -52,6 +52,11 @@ class LeafOpts(ctypes.Structure):
     _fields_ = [("rounds", ctypes.c_int32), ("cutoff", ctypes.c_double), ("tol", ctypes.c_double)]
 
 
+class LeafHeurOpts(ctypes.Structure):
+    """nep_leaf_heur_opts: the evaluator's per-round repair on the device (nep_leaf_eval_ex)"""
+    _fields_ = [("repair_every", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class ModelInfo(ctypes.Structure):
     _fields_ = [("n_int", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_tiles", ctypes.c_int32),
                 ("max_batch", ctypes.c_int32), ("x_entries", ctypes.c_int64), ("bytes_per_iter", ctypes.c_int64),
@@ -296,7 +301,8 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_bnb_incumbent_event", "nep_bnb_debug_ibound", "nep_bnb_create_engines", "nep_bnb_sync_get",
            "nep_bnb_sync_set", "nep_bnb_export_nodes", "nep_bnb_import_nodes", "nep_lp_get_reduced_costs",
            "nep_lp_rc_fixings", "nep_debug_block_split", "nep_leaf_eval", "nep_leaf_routing_entries",
-           "nep_debug_leaf_repair", "nep_bnb_set_leaf_engine", "nep_bnb_get_leaf_stats", "nep_bnb_incumbent_routing")
+           "nep_debug_leaf_repair", "nep_bnb_set_leaf_engine", "nep_bnb_get_leaf_stats", "nep_bnb_incumbent_routing",
+           "nep_leaf_eval_ex", "nep_debug_leaf_repair_from")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -391,6 +397,10 @@ def load_library(path=None):
     lib.nep_leaf_routing_entries.argtypes = [vp, i32, i64, pi64, pi32, pi32, _dp]
     lib.nep_debug_leaf_repair.argtypes = [ctypes.POINTER(ModelDesc), _dp, pi32, _dp, pi32, i64, pi64, pi32, pi32, _dp,
                                           _dp]
+    lib.nep_leaf_eval_ex.argtypes = [vp, i32, _dp, ctypes.POINTER(LeafOpts), ctypes.POINTER(LeafHeurOpts), _dp, _dp,
+                                     _dp, pi32, _dp, _dp, pi32, _dp, _dp]
+    lib.nep_debug_leaf_repair_from.argtypes = [ctypes.POINTER(ModelDesc), _dp, pi32, _dp, _dp, pi32, i64, pi64, pi32,
+                                               pi32, _dp, _dp]
     lib.nep_last_error.restype = ctypes.c_char_p
     lib.nep_api_version.restype = ctypes.c_int
     # array arguments travel as plain addresses (_ptr: the array's data pointer as an int): ctypes' typed
@@ -531,10 +541,11 @@ def debug_build(data, variant, step=STEP1, alpha=0.5, soften_step1_sol=1.3, max_
             "n_dual": n_dual}
 
 
-def debug_leaf_repair(data, variant, z, asg, alpha=0.5):
+def debug_leaf_repair(data, variant, z, asg, alpha=0.5, load=None):
     """Host-only (no GPU needed): the fixed-placement evaluator's repair (nep_debug_leaf_repair) of the step-1
-    placement z [n_int] from the assignment asg [R] (a destination per loaded routing row).  Returns (found, upper,
-    (row, dst, val), cpu [N])."""
+    placement z [n_int] from the assignment asg [R] (a destination per loaded routing row).  load [N] (None: summed
+    from asg in row order): the CPU loads of asg the moves start from (nep_debug_leaf_repair_from), as the evaluator
+    repairs a later round from that round's loads.  Returns (found, upper, (row, dst, val), cpu [N])."""
     lib = load_library()
     N, F = len(data.nodes), len(data.functions)
     v = VARIANTS[variant] if isinstance(variant, str) else int(variant)
@@ -544,16 +555,25 @@ def debug_leaf_repair(data, variant, z, asg, alpha=0.5):
     asg = np.ascontiguousarray(asg, np.int32)
     upper, found, cnt = np.zeros(1), np.zeros(1, np.int32), np.zeros(1, np.int64)
     cpu = np.zeros(N)
-    _check(lib, lib.nep_debug_leaf_repair(ctypes.byref(d), _ptr(z), _ptr(asg, ctypes.c_int32), _ptr(upper),
-                                          _ptr(found, ctypes.c_int32), 0, _ptr(cnt, ctypes.c_int64), None, None, None,
-                                          _ptr(cpu)), "nep_debug_leaf_repair")
+    if load is None:
+        def call(cap, row, dst, val):
+            return lib.nep_debug_leaf_repair(ctypes.byref(d), _ptr(z), _ptr(asg, ctypes.c_int32), _ptr(upper),
+                                             _ptr(found, ctypes.c_int32), cap, _ptr(cnt, ctypes.c_int64), row, dst,
+                                             val, _ptr(cpu))
+        name = "nep_debug_leaf_repair"
+    else:
+        load = np.ascontiguousarray(np.asarray(load, np.float64).reshape(N))
+
+        def call(cap, row, dst, val):
+            return lib.nep_debug_leaf_repair_from(ctypes.byref(d), _ptr(z), _ptr(asg, ctypes.c_int32), _ptr(load),
+                                                  _ptr(upper), _ptr(found, ctypes.c_int32), cap,
+                                                  _ptr(cnt, ctypes.c_int64), row, dst, val, _ptr(cpu))
+        name = "nep_debug_leaf_repair_from"
+    _check(lib, call(0, None, None, None), name)
     n = int(cnt[0])
     row, dst, val = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n)
     if n:
-        _check(lib, lib.nep_debug_leaf_repair(ctypes.byref(d), _ptr(z), _ptr(asg, ctypes.c_int32), _ptr(upper),
-                                              _ptr(found, ctypes.c_int32), n, _ptr(cnt, ctypes.c_int64),
-                                              _ptr(row, ctypes.c_int32), _ptr(dst, ctypes.c_int32), _ptr(val),
-                                              _ptr(cpu)), "nep_debug_leaf_repair")
+        _check(lib, call(n, _ptr(row, ctypes.c_int32), _ptr(dst, ctypes.c_int32), _ptr(val)), name)
     return bool(found[0]), float(upper[0]), (row, dst, val), cpu
 
 
@@ -743,21 +763,37 @@ class LPModel:
                                                           _ptr(idx, ctypes.c_int32), _ptr(val)), "nep_lp_rc_fixings")
         return idx, val
 
-    def leaf_eval(self, z, rounds=32, cutoff=math.inf, prices=None, tol=0.0):
+    def leaf_eval(self, z, rounds=32, cutoff=math.inf, prices=None, tol=0.0, repair_every=None):
         """The fixed-placement evaluator (nep_leaf_eval) on placements z [n, n_int] (every c and n 0 or 1) of a
         step-1 reference model: dict of lower [n] (Lagrangian bound on the leaf LP, best of rounds 0 .. rounds),
         upper [n] (objective of a repaired feasible routing, inf: none), status [n] (LEAF_*), prices [n, N] (behind
-        lower) and cpu [n, N] (loads of the returned routing).  prices [n, N] >= 0: the round-0 prices."""
+        lower) and cpu [n, N] (loads of the returned routing).  prices [n, N] >= 0: the round-0 prices.
+        repair_every = k (nep_leaf_eval_ex; None: nep_leaf_eval): the device also repairs the assignments of rounds
+        k, 2k, ... and the last one (0: none, nep_leaf_eval's results) and the cheaper of the best round's and round
+        0's host-verified point is returned; the dict then also has upper_round [n] (the round behind upper, -1 none),
+        device_upper [n] (the device's best objective, inf: none) and round_upper [n, rounds + 1] (the device's
+        objective per round, inf: not repaired or no point)."""
         z = np.ascontiguousarray(np.asarray(z, np.float64).reshape(-1, self.n_int))
         n = len(z)
         pin = None if prices is None else np.ascontiguousarray(np.asarray(prices, np.float64).reshape(n, self.N))
         lower, upper, status = np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
         pout, cpu = np.zeros((n, self.N)), np.zeros((n, self.N))
         opts = LeafOpts(int(rounds), float(cutoff), float(tol))
-        _check(self._lib, self._lib.nep_leaf_eval(self._h, n, _ptr(z), ctypes.byref(opts), _ptr(pin), _ptr(lower),
-                                                  _ptr(upper), _ptr(status, ctypes.c_int32), _ptr(pout), _ptr(cpu)),
-               "nep_leaf_eval")
-        return {"lower": lower, "upper": upper, "status": status, "prices": pout, "cpu": cpu}
+        if repair_every is None:
+            _check(self._lib, self._lib.nep_leaf_eval(self._h, n, _ptr(z), ctypes.byref(opts), _ptr(pin), _ptr(lower),
+                                                      _ptr(upper), _ptr(status, ctypes.c_int32), _ptr(pout),
+                                                      _ptr(cpu)), "nep_leaf_eval")
+            return {"lower": lower, "upper": upper, "status": status, "prices": pout, "cpu": cpu}
+        heur = LeafHeurOpts(int(repair_every), 0)
+        rnd, dev = np.zeros(n, np.int32), np.zeros(n)
+        per = np.zeros((n, max(0, int(rounds)) + 1))
+        _check(self._lib, self._lib.nep_leaf_eval_ex(self._h, n, _ptr(z), ctypes.byref(opts), ctypes.byref(heur),
+                                                     _ptr(pin), _ptr(lower), _ptr(upper),
+                                                     _ptr(status, ctypes.c_int32), _ptr(pout), _ptr(cpu),
+                                                     _ptr(rnd, ctypes.c_int32), _ptr(dev), _ptr(per)),
+               "nep_leaf_eval_ex")
+        return {"lower": lower, "upper": upper, "status": status, "prices": pout, "cpu": cpu, "upper_round": rnd,
+                "device_upper": dev, "round_upper": per}
 
     def leaf_routing(self, k):
         """(row, dst, val) of the routing behind upper[k] of the last leaf_eval call (nep_leaf_routing_entries;

@@ -93,7 +93,7 @@ class NeptuneStepBase(Solver):
     strengthen = True
 
     # the native tree's use of the fixed-placement evaluator (core/engine/bnb.py leaf_eval): off until
-    # its product runs are weighed
+    # its product runs are weighed (1 / True: on; 2: with every round's assignment repaired on the device as well)
     leaf_eval = False
 
     # bound-model slots beyond the `batch` in flight and its root's: finished branching nodes' states stay there
@@ -291,7 +291,7 @@ class NeptuneStepBase(Solver):
                   # step 1: warm starts banded around 8 x the model's cold-start primal weight
                   warm_weight_ref=8.0 if self.step_id() == _lp.STEP1 else 0.0,
                   step2_native=self.native_bound(), branching=self.branching,
-                  leaf_eval=bool(self.leaf_eval) and self.step_id() == _lp.STEP1)
+                  leaf_eval=int(self.leaf_eval) if self.step_id() == _lp.STEP1 else 0)
         kw.update(overrides)
         return BranchAndBound(model, data.workload_matrix, data.function_memory_matrix, data.node_memory_matrix, **kw)
 

@@ -1409,6 +1409,15 @@ void *nep_bnb_create_engines(const nep_bnb_engine *leaf, const nep_bnb_engine *b
   return t;
 }
 
+// params.leaf_eval = 2: the evaluator with every round's assignment repaired on the device (nep_leaf_eval_ex)
+static int leaf_eval_every_round(void *ctx, int32_t n, const double *z_leaf, const nep_leaf_opts *opts,
+                                 const double *prices_in, double *lower, double *upper, int32_t *status,
+                                 double *prices_out, double *cpu) {
+  const nep_leaf_heur_opts heur{1, 0};
+  return nep_leaf_eval_ex(ctx, n, z_leaf, opts, &heur, prices_in, lower, upper, status, prices_out, cpu, nullptr,
+                          nullptr, nullptr);
+}
+
 void *nep_bnb_create(void *leaf_model, void *bound_model, const nep_bnb_params *params, const double *fn_mem,
                      const double *node_mem) {
   if (!leaf_model) {
@@ -1420,7 +1429,8 @@ void *nep_bnb_create(void *leaf_model, void *bound_model, const nep_bnb_params *
   if (bound_model && model_ops(bound_model, &be)) return nullptr;
   void *tree = nep_bnb_create_engines(&le, bound_model ? &be : nullptr, params, fn_mem, node_mem);
   if (tree && nep::model_has_leaf_eval(leaf_model))
-    nep_bnb_set_leaf_engine(tree, leaf_model, nep_leaf_eval, nep_leaf_routing_entries);
+    nep_bnb_set_leaf_engine(tree, leaf_model, params && params->leaf_eval == 2 ? leaf_eval_every_round : nep_leaf_eval,
+                            nep_leaf_routing_entries);
   return tree;
 }
 

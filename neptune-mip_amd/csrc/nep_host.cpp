@@ -25,7 +25,7 @@
 #include "nep_leaf.h"
 
 namespace nep {
-hipError_t launch_leaf_rounds(const LeafView &v, int rounds, int threads, hipStream_t s);
+hipError_t launch_leaf_rounds(const LeafView &v, int rounds, int threads, hipStream_t s, const LeafHeurView *heur);
 hipError_t launch_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
                          bool plain, int it, hipStream_t s, int policy_slots = 0);
 int block_tile_waves(const DeviceView &v, int nslots, bool check);
@@ -240,6 +240,16 @@ struct Model {
     double *h_y = nullptr, *h_load = nullptr;
     int32_t *h_asg0 = nullptr;
     std::vector<LeafPoint> points;
+    // the per-round repair (nep_leaf_eval_ex with repair_every >= 1; nep_leaf_heur.hip), from its first use on: the
+    // device arrays, the pinned staging of the best round's [best | loadrep | asgrep] and of round_upper (which grows
+    // with the call's rounds)
+    bool heur = false;
+    LeafHeurView hv{};
+    void *pinned_h = nullptr, *pinned_ru = nullptr;
+    LeafHeurBest *h_best = nullptr;
+    double *h_loadrep = nullptr, *h_ru = nullptr;
+    int32_t *h_asgrep = nullptr;
+    int ru_stride = 0;   // round_upper holds [cap][ru_stride]
   };
   std::unique_ptr<LeafWork> leaf;
   // pinned staging of nep_lp_submit's uploads (slots, change offsets / indices / bounds, exact flags): the
@@ -261,6 +271,8 @@ struct Model {
     if (h_sols) (void)hipHostFree(h_sols);
     if (h_rc) (void)hipHostFree(h_rc);
     if (leaf && leaf->pinned) (void)hipHostFree(leaf->pinned);
+    if (leaf && leaf->pinned_h) (void)hipHostFree(leaf->pinned_h);
+    if (leaf && leaf->pinned_ru) (void)hipHostFree(leaf->pinned_ru);
     for (int k = 0; k < 2; ++k) {
       if (h_sub_i[k]) (void)hipHostFree(h_sub_i[k]);
       if (h_sub_d[k]) (void)hipHostFree(h_sub_d[k]);
@@ -2737,12 +2749,78 @@ static int ensure_leaf_alloc(Model &m) {
   return NEP_OK;
 }
 
+// the per-round repair's workspace (nep_leaf_heur.hip), on the first call that asks for it: the open lists, the
+// repair's state and the best round's copies for one chunk, and round_upper for `rounds` rounds
+static int ensure_leaf_heur(Model &m, int rounds) {
+  Model::LeafWork &w = *m.leaf;
+  const size_t N = m.N, F = m.F, R = m.R, B = w.cap;
+  if (!w.heur) {
+    const size_t n0 = m.allocs.size();
+    LeafHeurView h{};
+    std::vector<int32_t> rf(m.row_f.begin(), m.row_f.end());
+    int rc = upload(m, &h.row_f, rf);
+    if (!rc) rc = dalloc(m, &h.opl, B * F * N);
+    if (!rc) rc = dalloc(m, &h.opn, B * F);
+    if (!rc) rc = dalloc(m, &h.flow, B * R);
+    if (!rc) rc = dalloc(m, &h.room, B * F);
+    if (!rc) rc = dalloc(m, &h.fcost, B * F);
+    if (!rc) rc = dalloc(m, &h.nrows, B * R);
+    if (!rc) rc = dalloc(m, &h.asgrep, B * R);
+    if (!rc) rc = dalloc(m, &h.loadrep, B * N);
+    if (!rc) rc = dalloc(m, &h.best, B);
+    // pinned: [best | loadrep | asgrep]
+    void *pin = nullptr;
+    if (!rc && hipHostMalloc(&pin, B * (sizeof(LeafHeurBest) + N * sizeof(double) + R * sizeof(int32_t)) + 64) !=
+                   hipSuccess)
+      rc = fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, per-round repair)");
+    if (rc) {
+      while (m.allocs.size() > n0) {
+        (void)hipFree(m.allocs.back());
+        m.allocs.pop_back();
+      }
+      return rc;
+    }
+    h.floor_ = 1.0 - m.eps;
+    w.hv = h;
+    w.pinned_h = pin;
+    char *p = static_cast<char *>(pin);
+    w.h_best = reinterpret_cast<LeafHeurBest *>(p); p += B * sizeof(LeafHeurBest);
+    w.h_loadrep = reinterpret_cast<double *>(p); p += B * N * sizeof(double);
+    w.h_asgrep = reinterpret_cast<int32_t *>(p);
+    w.heur = true;
+  }
+  if (rounds + 1 > w.ru_stride) {
+    double *d = nullptr;
+    void *pin = nullptr;
+    const int rc = dalloc(m, &d, B * (size_t)(rounds + 1));
+    if (rc) return rc;
+    if (hipHostMalloc(&pin, B * (size_t)(rounds + 1) * sizeof(double)) != hipSuccess)
+      return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, round_upper)");
+    if (w.pinned_ru) (void)hipHostFree(w.pinned_ru);
+    w.pinned_ru = pin;
+    w.h_ru = static_cast<double *>(pin);
+    w.hv.round_upper = d;   // (an earlier, shorter one stays with the model's allocations)
+    w.ru_stride = rounds + 1;
+  }
+  return NEP_OK;
+}
+
 int nep_leaf_eval(void *model, int32_t n, const double *z_leaf, const nep_leaf_opts *opts, const double *prices_in,
                   double *lower, double *upper, int32_t *status, double *prices_out, double *cpu) {
+  return nep_leaf_eval_ex(model, n, z_leaf, opts, nullptr, prices_in, lower, upper, status, prices_out, cpu, nullptr,
+                          nullptr, nullptr);
+}
+
+int nep_leaf_eval_ex(void *model, int32_t n, const double *z_leaf, const nep_leaf_opts *opts,
+                     const nep_leaf_heur_opts *heur, const double *prices_in, double *lower, double *upper,
+                     int32_t *status, double *prices_out, double *cpu, int32_t *upper_round, double *device_upper,
+                     double *round_upper) {
   if (!model || !z_leaf || !lower || !upper || !status) return fail(NEP_ERR_ARG, "null argument");
   Model &m = *static_cast<Model *>(model);
   if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
   if (n < 1) return fail(NEP_ERR_ARG, "n must be at least 1");
+  const int every = heur ? heur->repair_every : 0;
+  if (every < 0) return fail(NEP_ERR_ARG, "repair_every must be >= 0");
   const int rounds = opts ? opts->rounds : 32;
   const double cutoff = opts ? opts->cutoff : INF;
   const double tol = opts && opts->tol > 0.0 ? opts->tol : 1e-6;
@@ -2756,9 +2834,16 @@ int nep_leaf_eval(void *model, int32_t n, const double *z_leaf, const nep_leaf_o
     if (!(prices_in[k] >= 0.0) || prices_in[k] == INF) return fail(NEP_ERR_ARG, "prices_in must be finite and >= 0");
   int rc = ensure_leaf(m);
   if (rc) return rc;
+  if (every && (rc = ensure_leaf_heur(m, rounds))) return rc;
   Model::LeafWork &w = *m.leaf;
   w.points.assign(n, LeafPoint());
   const LeafInstance in = leaf_instance(m);
+  const size_t nr = (size_t)rounds + 1;
+  for (int b = 0; b < n; ++b) {
+    if (upper_round) upper_round[b] = -1;
+    if (device_upper) device_upper[b] = INF;
+    if (round_upper) std::fill(round_upper + b * nr, round_upper + (b + 1) * nr, INF);
+  }
   std::vector<uint8_t> c_open(F * N);
   std::vector<int> todo;   // the placements that reach the device
   for (int b = 0; b < n; ++b) {
@@ -2794,16 +2879,29 @@ int nep_leaf_eval(void *model, int32_t n, const double *z_leaf, const nep_leaf_o
     HIPCHK(hipMemcpyAsync(v.ctrl, w.h_ctrl, B * sizeof(LeafCtrl), hipMemcpyHostToDevice, m.aux));
     HIPCHK(hipMemcpyAsync(v.y, w.h_y, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
     HIPCHK(hipMemcpyAsync(v.ybest, w.h_y, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
-    HIPCHK(launch_leaf_rounds(v, rounds, w.threads, m.aux));
+    LeafHeurView hv = w.hv;
+    hv.rounds = rounds;
+    hv.every = every;
+    HIPCHK(launch_leaf_rounds(v, rounds, w.threads, m.aux, every ? &hv : nullptr));
     // one read at the end: bounds and flags, the best prices, the last loads, the round-0 assignment
     HIPCHK(hipMemcpyAsync(w.h_ctrl, v.ctrl, B * sizeof(LeafCtrl), hipMemcpyDeviceToHost, m.aux));
     HIPCHK(hipMemcpyAsync(w.h_y, v.ybest, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
     HIPCHK(hipMemcpyAsync(w.h_load, v.load, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
     HIPCHK(hipMemcpyAsync(w.h_asg0, v.asg0, B * R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+    if (every) {   // the best repaired round: its objective and number, its loads and assignment; the rounds' verdicts
+      HIPCHK(hipMemcpyAsync(w.h_best, hv.best, B * sizeof(LeafHeurBest), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_loadrep, hv.loadrep, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_asgrep, hv.asgrep, B * R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_ru, hv.round_upper, B * nr * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    }
     HIPCHK(hipStreamSynchronize(m.aux));
     for (int q = 0; q < B; ++q) {
       const int b = todo[t0 + q];
       const LeafCtrl &c = w.h_ctrl[q];
+      if (every) {
+        if (device_upper) device_upper[b] = w.h_best[q].obj;
+        if (round_upper) std::memcpy(round_upper + b * nr, w.h_ru + q * nr, nr * sizeof(double));
+      }
       lower[b] = c.best;
       upper[b] = INF;
       if (prices_out) std::memcpy(prices_out + b * N, w.h_y + q * N, N * sizeof(double));
@@ -2814,6 +2912,17 @@ int nep_leaf_eval(void *model, int32_t n, const double *z_leaf, const nep_leaf_o
       }
       LeafPoint &pt = w.points[b];
       leaf_repair(in, w.h_open + q * F * N, nsums[q], w.h_asg0 + q * R, pt);
+      int from = pt.found ? 0 : -1;
+      if (every && w.h_best[q].round >= 0) {
+        // the device chose the round; its point is the host's, verified in fp64, from the loads the device started at
+        LeafPoint alt;
+        leaf_repair(in, w.h_open + q * F * N, nsums[q], w.h_asgrep + q * R, alt, w.h_loadrep + q * N);
+        if (alt.found && (!pt.found || alt.obj < pt.obj)) {
+          pt = std::move(alt);
+          from = w.h_best[q].round;
+        }
+      }
+      if (upper_round) upper_round[b] = from;
       if (!pt.found) {
         status[b] = NEP_LEAF_NO_POINT;
         continue;
@@ -2848,6 +2957,12 @@ int nep_leaf_routing_entries(void *model, int32_t k, int64_t capacity, int64_t *
 int nep_debug_leaf_repair(const nep_model_desc *desc, const double *z_leaf, const int32_t *asg, double *upper,
                           int32_t *found, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst, double *val,
                           double *cpu) {
+  return nep_debug_leaf_repair_from(desc, z_leaf, asg, nullptr, upper, found, capacity, n_entries, row, dst, val, cpu);
+}
+
+int nep_debug_leaf_repair_from(const nep_model_desc *desc, const double *z_leaf, const int32_t *asg, const double *load,
+                               double *upper, int32_t *found, int64_t capacity, int64_t *n_entries, int32_t *row,
+                               int32_t *dst, double *val, double *cpu) {
   if (!desc || !z_leaf || !asg || !upper || !found || !n_entries) return fail(NEP_ERR_ARG, "null argument");
   if (desc->device_inputs) return fail(NEP_ERR_ARG, "nep_debug_leaf_repair takes host arrays (device_inputs = 0)");
   Model m;
@@ -2862,7 +2977,7 @@ int nep_debug_leaf_repair(const nep_model_desc *desc, const double *z_leaf, cons
   *upper = INF;
   *n_entries = 0;
   if (leaf_rejects(m, z_leaf, c_open.data())) return NEP_OK;
-  leaf_repair(leaf_instance(m), c_open.data(), nsum, asg, pt);
+  leaf_repair(leaf_instance(m), c_open.data(), nsum, asg, pt, load);
   if (cpu && !pt.cpu.empty()) std::memcpy(cpu, pt.cpu.data(), m.N * sizeof(double));
   if (!pt.found) return NEP_OK;
   *found = 1;

@@ -46,6 +46,36 @@ struct LeafView {
   LeafCtrl *ctrl;        // [B]
 };
 
+// The per-round repair on the device (nep_leaf_heur.hip; nep_leaf_eval_ex with repair_every >= 1): moves of one round's
+// repair at most, far below the host repair's 100000 — a round that needs more has no point.  The kernel's loops are
+// bounded by this, N, F and R only.
+constexpr int kLeafDevMoves = 4096;
+
+// per-placement result of the device repairs
+struct LeafHeurBest {
+  double obj;       // the smallest objective a round's repair ended with (+inf: none)
+  int32_t round;    // that round (-1: none); ties keep the earlier round
+  int32_t pad_;
+};
+
+// device arrays of the per-round repair, one chunk of placements; the per-(f, j) column counts live in LeafView::share,
+// dead between leaf_node and the next round's leaf_assign
+struct LeafHeurView {
+  int rounds;                // the call's rounds: round_upper's stride is rounds + 1
+  int every;                 // repair rounds every, 2 every, ... and the last one
+  double floor_;             // the column floor 1 - eps
+  const int32_t *row_f;      // [R]
+  uint16_t *opl;             // [B][F][N] the placements' open destinations per function, ascending
+  int32_t *opn;              // [B][F] their counts
+  double *flow;              // [B][R] flow left per row at its assigned node
+  double *room, *fcost;      // [B][F] pooled mass left after the column deficits; the assignment's cost by function
+  int32_t *nrows;            // [B][R] rows by overloaded node
+  int32_t *asgrep;           // [B][R] the assignment of the best round
+  double *loadrep;           // [B][N] its loads
+  LeafHeurBest *best;        // [B]
+  double *round_upper;       // [B][rounds + 1] objective per repaired round (+inf: not repaired, or no point)
+};
+
 // the host's fp64 view of a step-1 instance
 struct LeafInstance {
   int N, F, R, has_n;
@@ -62,7 +92,9 @@ struct LeafPoint {
   std::vector<double> val, cpu;
 };
 
-// host repair of an assignment asg [R] (destination per loaded row) at the placement c_open [F][N] with nsum open nodes
-void leaf_repair(const LeafInstance &in, const uint8_t *c_open, double nsum, const int32_t *asg, LeafPoint &out);
+// host repair of an assignment asg [R] (destination per loaded row) at the placement c_open [F][N] with nsum open nodes;
+// load [N] (or nullptr: summed here from asg in row order) are the CPU loads of asg the moves start from
+void leaf_repair(const LeafInstance &in, const uint8_t *c_open, double nsum, const int32_t *asg, LeafPoint &out,
+                 const double *load = nullptr);
 
 }  // namespace nep

@@ -13,6 +13,8 @@
 //                y_j = 0 and g_j < 0)
 //   leaf_step    per placement: L, the best bound and its prices, the cutoff test, the step (nep_leaf.h) and
 //                y <- max(0, y + theta g)
+// (nep_leaf_eval_ex with repair_every >= 1 adds, between leaf_node and leaf_step of the selected rounds, the repair of
+// the round's assignment: nep_leaf_heur.hip.)
 // The rounds of a call are enqueued back to back; a placement that is cut off, or whose subgradient vanished (its
 // prices are optimal), sets `done` and its blocks return at once in later rounds.  No atomics: every sum has a fixed
 // order, so two calls on the same input return the same bits.  The working set (D, W, cpr, a chunk's shares) is L2
@@ -217,12 +219,24 @@ __global__ void leaf_step(LeafView v, int last) {
   }
 }
 
-// the rounds 0 .. rounds of a chunk, back to back on s; `threads`: leaf_assign's workgroup (64, 128 or 256)
-hipError_t launch_leaf_rounds(const LeafView &v, int rounds, int threads, hipStream_t s) {
+hipError_t launch_leaf_heur_init(const LeafView &v, const LeafHeurView &h, hipStream_t s);    // nep_leaf_heur.hip
+hipError_t launch_leaf_repair(const LeafView &v, const LeafHeurView &h, int rd, hipStream_t s);
+
+// the rounds 0 .. rounds of a chunk, back to back on s; `threads`: leaf_assign's workgroup (64, 128 or 256); heur (or
+// nullptr): the per-round repair of nep_leaf_heur.hip, serial in the round between leaf_node and leaf_step
+hipError_t launch_leaf_rounds(const LeafView &v, int rounds, int threads, hipStream_t s, const LeafHeurView *heur) {
   const size_t lds = leaf_assign_lds(v.N);
+  if (heur) {
+    const hipError_t e = launch_leaf_heur_init(v, *heur, s);
+    if (e != hipSuccess) return e;
+  }
   for (int rd = 0; rd <= rounds; ++rd) {
     hipLaunchKernelGGL(leaf_assign, dim3(v.F, v.B), dim3(threads), lds, s, v, rd == 0 ? v.asg0 : v.asg);
     hipLaunchKernelGGL(leaf_node, dim3((v.N + 255) / 256, v.B), dim3(256), 0, s, v);
+    if (heur && ((rd > 0 && rd % heur->every == 0) || rd == rounds)) {
+      const hipError_t e = launch_leaf_repair(v, *heur, rd, s);
+      if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(leaf_step, dim3(v.B), dim3(kLeafThreads), 0, s, v, rd == rounds ? 1 : 0);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -36,7 +36,8 @@ inline int find(const std::vector<Ent> &e, int j) {
 }
 }  // namespace
 
-void leaf_repair(const LeafInstance &in, const uint8_t *c_open, double nsum, const int32_t *asg, LeafPoint &out) {
+void leaf_repair(const LeafInstance &in, const uint8_t *c_open, double nsum, const int32_t *asg, LeafPoint &out,
+                 const double *load) {
   const int N = in.N, F = in.F, R = in.R;
   const double floor_ = 1.0 - in.eps;
   out = LeafPoint();
@@ -57,10 +58,13 @@ void leaf_repair(const LeafInstance &in, const uint8_t *c_open, double nsum, con
       return;
     }
     ent[r].push_back(Ent{j, 1.0});
-    cpu[j] += in.W[(size_t)f * N + i] * in.cpr[(size_t)f * N + j];
+    if (!load) cpu[j] += in.W[(size_t)f * N + i] * in.cpr[(size_t)f * N + j];
     col[(size_t)f * N + j] += 1.0;
     node_rows[j].push_back(r);
   }
+  // (the device rounds' loads, summed per function and then over the functions: the moves then see the bits the
+  // device repair saw; the returned point's loads are recomputed from its entries either way)
+  if (load) std::copy(load, load + N, cpu.begin());
   for (int f = 0; f < F; ++f) {
     const int rl = in.frow[f + 1] - 1;
     const bool pooled = in.frow[f + 1] > in.frow[f] && in.row_src[rl] < 0;
