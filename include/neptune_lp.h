@@ -310,6 +310,39 @@ int nep_leaf_eval_ex(void *model, int32_t n, const double *z_leaf /* [n][n_int] 
                      int32_t *status, double *prices_out, double *cpu, int32_t *upper_round /* [n] or NULL */,
                      double *device_upper /* [n] or NULL */, double *round_upper /* [n][rounds + 1] or NULL */);
 
+/* Priced moves of fixed placements (csrc/nep_leaf_moves.hip, csrc/nep_leaf_moves.cpp; DESIGN.md §7 "Priced moves"): the
+ * exact change of the Lagrangian bound L(C, y) of nep_leaf_eval when one closed placement (f, j) opens or an open one
+ * closes, for every (f, j) of each placement at once, at given prices y >= 0 (NULL: zeros).  A loaded row r = (f, i)
+ * costs rho_r(j) = (kobj w) D[i, j] + w (y_j cpr[f, j]) at j; m1_r / j1_r are its minimum and argmin over the open
+ * destinations of f (ties to the lowest j), m2_r the minimum over the others (+inf: none).
+ *   table [n][F][N]  (f, j) closed: -sum_r max(0, m1_r - rho_r(j)) <= 0; (f, j) open: sum_{r: j1_r = j} (m2_r - m1_r)
+ *                    >= 0, +inf when it is the function's only destination; rows in ascending order (device, fp64)
+ *   lagr [n]         L(C, y): nep_leaf_eval's `lower` at rounds = 0 with prices_in = y
+ * The moves are composed and screened on the host from the table (a node is open when its column of c has a 1):
+ *   NEP_MOVE_ADD    a closed (f, j): delta = table + cost_n where the node opens (variants with n); kept only while the
+ *                   node's memory holds f too and an opened node's cost is within the budget (the INFEASIBLE rules)
+ *   NEP_MOVE_DROP   an open (f, j) with a finite entry: delta = table - cost_n where it is the node's only placement
+ *   NEP_MOVE_CLOSE  a node with at least two placements, all finite: delta = their entries summed in ascending f, minus
+ *                   cost_n; fn = -1
+ * and returned in ascending (delta, kind, node, fn) order, at most max_moves per placement (n_moves [n] of them; the
+ * rest of kind / fn / node is -1, of delta +inf).  Applying a move (ADD sets c and n_j; DROP clears c, and n_j with the
+ * column; CLOSE clears the column and n_j) gives a placement C' that passes the INFEASIBLE rules, with
+ * L(C', y) = L(C, y) + delta up to fp64 rounding.  A placement the evaluator rejects as INFEASIBLE gets n_moves = 0,
+ * lagr = +inf and a table of +inf.  max_moves = 0 (kind .. delta may be NULL) prices only.  Runs on the auxiliary
+ * stream in the evaluator's workspace, between evaluator calls; no slot state is read or written.  NEP_ERR_ARG as
+ * nep_leaf_eval (step-2 / facility models, an entry not 0 or 1, a negative price, a NULL required pointer), for
+ * max_moves < 0, and for a model of more than 1169 nodes: the kernel keeps 56 (N + 1) + 16 bytes of LDS per workgroup
+ * and is held to 64 KiB (nep_leaf_eval itself takes every admitted N). */
+enum { NEP_MOVE_ADD = 0, NEP_MOVE_DROP = 1, NEP_MOVE_CLOSE = 2 };
+int nep_leaf_moves(void *model, int32_t n, const double *z_leaf /* [n][n_int] */,
+                   const double *prices /* [n][N] >= 0, or NULL: zeros */, int32_t max_moves,
+                   int32_t *n_moves /* [n] */, int32_t *kind, int32_t *fn, int32_t *node, double *delta /* [n][max_moves] */,
+                   double *lagr /* [n] or NULL */, double *table /* [n][F][N] or NULL */);
+/* host-only: the move list of one placement from a given table (composition, screens, order), so the CPU suite
+ * checks it without a GPU, in the manner of nep_debug_leaf_repair */
+int nep_debug_leaf_move_list(const nep_model_desc *desc, const double *z_leaf, const double *table /* [F][N] */,
+                             int32_t max_moves, int32_t *n_moves, int32_t *kind, int32_t *fn, int32_t *node, double *delta);
+
 /* The reference's offline scorers and feasibility checkers on a slot's solution, on the device
  * (efttc/utils/objectives.py:23-98, efttc/utils/constraints_step1.py:5-133; booleans are the
  * reference's truthiness, value != 0).  out[NEP_SC_COUNT]: */

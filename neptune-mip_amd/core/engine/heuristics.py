@@ -8,6 +8,9 @@ a function without loaded sources gets the open node with memory room the LP pre
 placement then carries >= 1 unit of flow (C2, :5-15) and every source is routed (C4, :27-34), so the leaf LP
 has a feasible point — the greedy routing itself; more nodes are opened until the routing succeeds.  The
 node box's fixings are kept (closed nodes / placements excluded, fixed-open ones opened first).
+
+`placement_search` — local search over placements with the fixed-placement evaluator and its priced add / drop /
+close moves (nep_leaf_eval, nep_leaf_moves; DESIGN.md §7 "Priced moves"); `apply_move` applies one move.
 """
 import numpy as np
 
@@ -103,4 +106,81 @@ def capacity_greedy(W, D, cpr, cores, fmem, nmem, n_rank, flow=None, start=None,
                         (np.asarray(rf, np.int64), np.asarray(ri, np.int64), np.asarray(rj, np.int64))))
         k += step
     out.sort(key=lambda t: t[2])
+    return out
+
+
+def apply_move(z, F, N, has_n, kind, fn, node):
+    """z' = the placement z (c f-major [F N], then n [N] where the variant has n) after one priced move (nep_leaf_moves):
+    ADD (0) opens (fn, node) and the node; DROP (1) closes (fn, node), and the node with its last placement; CLOSE (2)
+    closes the node and every placement on it."""
+    z = np.array(z, np.float64, copy=True)
+    C = z[:F * N].reshape(F, N)
+    kind, fn, node = int(kind), int(fn), int(node)
+    if kind == 0:
+        C[fn, node] = 1.0
+        opened = 1.0
+    elif kind == 1:
+        C[fn, node] = 0.0
+        opened = 1.0 if C[:, node].any() else 0.0
+    elif kind == 2:
+        C[:, node] = 0.0
+        opened = 0.0
+    else:
+        raise ValueError(f"unknown move kind {kind}")
+    if has_n:
+        z[F * N + node] = opened
+    return z
+
+
+def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_passes=32, time_limit=None, warm=True,
+                     log=None):
+    """Local search over placements from z0 [n_int] with the fixed-placement evaluator and its priced moves (DESIGN.md
+    §7 "Priced moves").  model: anything with F, N, n_int and leaf_eval / leaf_moves / leaf_routing (LPModel's
+    contracts).  Per pass: the moves of the current placement at its evaluated prices, the first `width` applied, the
+    neighbours evaluated in one leaf_eval call cut off at the incumbent's upper (from the current prices when `warm`),
+    the best accepted when it improves upper by more than 1e-9 max(1, |upper|) (ties: the earlier move); a start
+    without a point takes the first neighbour that has one.  Stops at the first pass without an acceptance, at
+    max_passes or at time_limit seconds.  Deterministic.  Returns dict(z, upper, lower, row, dst, val (the routing
+    of z, None without a point), start_upper, passes, evaluated, accepted [(kind, fn, node, delta, upper)])."""
+    import time
+    F, N = int(model.F), int(model.N)
+    has_n = int(model.n_int) == F * N + N
+    t0 = time.monotonic() if time_limit is not None else 0.0
+    z = np.array(np.asarray(z0, np.float64).reshape(-1), copy=True)
+    r = model.leaf_eval(z[None, :], rounds=rounds, repair_every=repair_every)
+    upper, lower = float(r["upper"][0]), float(r["lower"][0])
+    prices = np.array(r["prices"][0], np.float64, copy=True)
+    entries = model.leaf_routing(0) if np.isfinite(upper) else (None, None, None)
+    out = {"start_upper": upper, "passes": 0, "evaluated": 0, "accepted": []}
+    while out["passes"] < max_passes and np.isfinite(lower):
+        if time_limit is not None and time.monotonic() - t0 >= time_limit:
+            break
+        mv = model.leaf_moves(z[None, :], prices=prices[None, :], max_moves=int(width))
+        k = int(mv["n_moves"][0])
+        if k == 0:
+            break
+        out["passes"] += 1
+        Z = np.stack([apply_move(z, F, N, has_n, mv["kind"][0, q], mv["fn"][0, q], mv["node"][0, q])
+                      for q in range(k)])
+        r = model.leaf_eval(Z, rounds=rounds, cutoff=upper, prices=np.tile(prices, (k, 1)) if warm else None,
+                            repair_every=repair_every)
+        out["evaluated"] += k
+        ups = np.asarray(r["upper"], np.float64)
+        if np.isfinite(upper):
+            q = int(np.argmin(ups))
+            if not ups[q] < upper - 1e-9 * max(1.0, abs(upper)):
+                break
+        else:
+            has = np.flatnonzero(np.isfinite(ups))
+            if has.size == 0:
+                break
+            q = int(has[0])
+        entries = model.leaf_routing(q)
+        z, upper, lower = Z[q], float(ups[q]), float(r["lower"][q])
+        prices = np.array(r["prices"][q], np.float64, copy=True)
+        out["accepted"].append((int(mv["kind"][0, q]), int(mv["fn"][0, q]), int(mv["node"][0, q]),
+                                float(mv["delta"][0, q]), upper))
+        if log is not None:
+            log(f"placement search: pass {out['passes']} move {out['accepted'][-1][:3]} upper {upper:.10g}")
+    out.update(z=z, upper=upper, lower=lower, row=entries[0], dst=entries[1], val=entries[2])
     return out

@@ -21,6 +21,7 @@ VARIANTS = {"MinDelay": MIN_DELAY, "MinUtilization": MIN_UTILIZATION,
 API_VERSION = 13
 RELAX_REFERENCE, RELAX_FACILITY = 0, 1
 LEAF_EXACT, LEAF_FEASIBLE, LEAF_NO_POINT, LEAF_INFEASIBLE, LEAF_CUTOFF = 0, 1, 2, 3, 4
+MOVE_ADD, MOVE_DROP, MOVE_CLOSE = 0, 1, 2
 
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -302,7 +303,7 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_bnb_sync_set", "nep_bnb_export_nodes", "nep_bnb_import_nodes", "nep_lp_get_reduced_costs",
            "nep_lp_rc_fixings", "nep_debug_block_split", "nep_leaf_eval", "nep_leaf_routing_entries",
            "nep_debug_leaf_repair", "nep_bnb_set_leaf_engine", "nep_bnb_get_leaf_stats", "nep_bnb_incumbent_routing",
-           "nep_leaf_eval_ex", "nep_debug_leaf_repair_from")
+           "nep_leaf_eval_ex", "nep_debug_leaf_repair_from", "nep_leaf_moves", "nep_debug_leaf_move_list")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -401,6 +402,8 @@ def load_library(path=None):
                                      _dp, pi32, _dp, _dp, pi32, _dp, _dp]
     lib.nep_debug_leaf_repair_from.argtypes = [ctypes.POINTER(ModelDesc), _dp, pi32, _dp, _dp, pi32, i64, pi64, pi32,
                                                pi32, _dp, _dp]
+    lib.nep_leaf_moves.argtypes = [vp, i32, _dp, _dp, i32, pi32, pi32, pi32, pi32, _dp, _dp, _dp]
+    lib.nep_debug_leaf_move_list.argtypes = [ctypes.POINTER(ModelDesc), _dp, _dp, i32, pi32, pi32, pi32, pi32, _dp]
     lib.nep_last_error.restype = ctypes.c_char_p
     lib.nep_api_version.restype = ctypes.c_int
     # array arguments travel as plain addresses (_ptr: the array's data pointer as an int): ctypes' typed
@@ -575,6 +578,29 @@ def debug_leaf_repair(data, variant, z, asg, alpha=0.5, load=None):
     if n:
         _check(lib, call(n, _ptr(row, ctypes.c_int32), _ptr(dst, ctypes.c_int32), _ptr(val)), name)
     return bool(found[0]), float(upper[0]), (row, dst, val), cpu
+
+
+def debug_leaf_move_list(data, variant, z, table, max_moves, alpha=0.5, step=STEP1, relaxation=RELAX_REFERENCE,
+                         max_score=0.0):
+    """Host-only (no GPU needed): the move list (nep_debug_leaf_move_list) of the step-1 placement z [n_int] from its
+    priced table [F, N] (nep_leaf_moves' composition, screens and order).  Returns dict(n_moves, kind, fn, node, delta)
+    with the arrays cut to n_moves."""
+    lib = load_library()
+    N, F = len(data.nodes), len(data.functions)
+    v = VARIANTS[variant] if isinstance(variant, str) else int(variant)
+    k = _arrays(data, N, F)
+    d = _desc(k, N, F, v, int(step), alpha, 1.3, max_score, 0.0, data.node_budget, relaxation)
+    z = np.ascontiguousarray(z, np.float64)
+    table = None if table is None else np.ascontiguousarray(np.asarray(table, np.float64).reshape(F, N))
+    mm = int(max_moves)
+    cnt = np.zeros(1, np.int32)
+    kind, fn, node = (np.zeros(max(mm, 0), np.int32) for _ in range(3))
+    delta = np.zeros(max(mm, 0))
+    _check(lib, lib.nep_debug_leaf_move_list(ctypes.byref(d), _ptr(z), _ptr(table), mm, _ptr(cnt, ctypes.c_int32),
+                                             _ptr(kind, ctypes.c_int32), _ptr(fn, ctypes.c_int32),
+                                             _ptr(node, ctypes.c_int32), _ptr(delta)), "nep_debug_leaf_move_list")
+    n = int(cnt[0])
+    return {"n_moves": n, "kind": kind[:n], "fn": fn[:n], "node": node[:n], "delta": delta[:n]}
 
 
 def debug_block_split(n_nodes, n_functions, na, relaxation=RELAX_REFERENCE):
@@ -794,6 +820,29 @@ class LPModel:
                "nep_leaf_eval_ex")
         return {"lower": lower, "upper": upper, "status": status, "prices": pout, "cpu": cpu, "upper_round": rnd,
                 "device_upper": dev, "round_upper": per}
+
+    def leaf_moves(self, z, prices=None, max_moves=64, table=False):
+        """The priced moves (nep_leaf_moves) of placements z [n, n_int] of a step-1 reference model at prices [n, N]
+        >= 0 (None: zeros): dict of n_moves [n], kind / fn / node [n, max_moves] (MOVE_ADD / MOVE_DROP / MOVE_CLOSE;
+        the function, -1 for CLOSE; the node; -1 past n_moves), delta [n, max_moves] (the exact change of the
+        Lagrangian bound at these prices, ascending; inf past n_moves), lagr [n] (that bound) and, with table=True,
+        table [n, F, N] (the routing part of the change per (f, j): <= 0 to open a closed one, >= 0 to close an open
+        one, inf for a function's only destination)."""
+        z = np.ascontiguousarray(np.asarray(z, np.float64).reshape(-1, self.n_int))
+        n, mm = len(z), int(max_moves)
+        pin = None if prices is None else np.ascontiguousarray(np.asarray(prices, np.float64).reshape(n, self.N))
+        cnt = np.zeros(n, np.int32)
+        kind, fn, node = (np.zeros((n, max(mm, 0)), np.int32) for _ in range(3))
+        delta, lagr = np.zeros((n, max(mm, 0))), np.zeros(n)
+        tab = np.zeros((n, self.F, self.N)) if table else None
+        _check(self._lib, self._lib.nep_leaf_moves(self._h, n, _ptr(z), _ptr(pin), mm, _ptr(cnt, ctypes.c_int32),
+                                                   _ptr(kind, ctypes.c_int32), _ptr(fn, ctypes.c_int32),
+                                                   _ptr(node, ctypes.c_int32), _ptr(delta), _ptr(lagr), _ptr(tab)),
+               "nep_leaf_moves")
+        out = {"n_moves": cnt, "kind": kind, "fn": fn, "node": node, "delta": delta, "lagr": lagr}
+        if table:
+            out["table"] = tab
+        return out
 
     def leaf_routing(self, k):
         """(row, dst, val) of the routing behind upper[k] of the last leaf_eval call (nep_leaf_routing_entries;

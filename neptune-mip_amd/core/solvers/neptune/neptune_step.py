@@ -20,7 +20,7 @@ import numpy as np
 
 from ...engine import lp as _lp
 from ...engine.bnb import OPTIMAL, BranchAndBound
-from ...engine.heuristics import capacity_greedy
+from ...engine.heuristics import capacity_greedy, placement_search
 from ...engine.routing import SparseRouting, repair_cpu
 from ..solver import Solver
 
@@ -95,6 +95,11 @@ class NeptuneStepBase(Solver):
     # the native tree's use of the fixed-placement evaluator (core/engine/bnb.py leaf_eval): off until
     # its product runs are weighed (1 / True: on; 2: with every round's assignment repaired on the device as well)
     leaf_eval = False
+
+    # local search over placements at the root (core/engine/heuristics.py placement_search; DESIGN.md §7 "Priced
+    # moves"): 0 off; a width > 0: from the cheapest capacity-greedy leaf, that many priced moves evaluated per pass,
+    # its end point appended to the root's primal items.  Off until its product runs are weighed over more seeds
+    placement_search = 0
 
     # bound-model slots beyond the `batch` in flight and its root's: finished branching nodes' states stay there
     # (least recently finished reused first) so their children warm-start from them (DESIGN.md §7 "Parked parents")
@@ -212,6 +217,45 @@ class NeptuneStepBase(Solver):
         z[n0:n1] = n
         return {"objective": obj, "z": z, "row": np.arange(len(rf)), "dst": dst, "val": np.ones(len(rf))}
 
+    def _with_placement_search(self, primal, model, layout, row_map):
+        """primal, with the root call (no fixings) followed by placement_search on the leaf model from the cheapest
+        capacity-greedy placement: one more item (idx, val, sol), sol from the evaluator's host-verified routing when
+        it passes check_placement in fp64, else None.  A search that accepts no move adds nothing: its end point is
+        the greedy's first item, which is already there."""
+        d = self.data
+        F, N = len(d.functions), len(d.nodes)
+        c0, c1 = layout["c"]
+        n0, n1 = layout["n"]
+        W = np.asarray(d.workload_matrix, np.float64)
+        rf, rs = (np.asarray(a) for a in row_map)
+
+        def wrapped(idx, val, z, flow):
+            items = list(primal(idx, val, z, flow))
+            if len(idx) or not items:
+                return items
+            z0 = np.zeros(model.n_int)
+            z0[np.asarray(items[0][0])] = items[0][1]
+            res = placement_search(model, z0, width=int(self.placement_search), log=self.log)
+            if not res["accepted"]:
+                return items
+            zs = res["z"]
+            C, n = zs[c0:c1].reshape(F, N), zs[n0:n1]
+            sol = None
+            if res["row"] is not None:
+                x_fij = np.zeros((F, N, N))
+                for r, j, v in zip(res["row"].tolist(), res["dst"].tolist(), res["val"].tolist()):
+                    f, i = int(rf[r]), int(rs[r])
+                    if i >= 0:
+                        x_fij[f, i, j] = v
+                    else:
+                        x_fij[f, W[f] == 0, j] = v
+                if self.check_placement(C, n, x_fij):
+                    sol = {"objective": res["upper"], "z": zs, "row": res["row"], "dst": res["dst"],
+                           "val": res["val"]}
+            items.append((np.concatenate([np.arange(c0, c1), np.arange(n0, n1)]), np.concatenate([C.ravel(), n]), sol))
+            return items
+        return wrapped
+
     def check_placement(self, C, n, x):
         """Every step-1 row of the reference (constraints_step1.py) at an integral point, in fp64: C1/C2 (flow
         only into open placements, >= 1 - eps into each), C3 memory, C4 each source routed once, C5 CPU
@@ -292,6 +336,10 @@ class NeptuneStepBase(Solver):
                   warm_weight_ref=8.0 if self.step_id() == _lp.STEP1 else 0.0,
                   step2_native=self.native_bound(), branching=self.branching,
                   leaf_eval=int(self.leaf_eval) if self.step_id() == _lp.STEP1 else 0)
+        row_map = _row_map(model)
+        if (int(self.placement_search) > 0 and self.step_id() == _lp.STEP1 and kw["primal"] is not None
+                and row_map is not None and hasattr(model, "leaf_moves")):
+            kw["primal"] = self._with_placement_search(kw["primal"], model, layout, row_map)
         kw.update(overrides)
         return BranchAndBound(model, data.workload_matrix, data.function_memory_matrix, data.node_memory_matrix, **kw)
 

@@ -26,6 +26,8 @@
 
 namespace nep {
 hipError_t launch_leaf_rounds(const LeafView &v, int rounds, int threads, hipStream_t s, const LeafHeurView *heur);
+hipError_t launch_leaf_moves(const LeafView &v, int threads, hipStream_t s);   // nep_leaf_moves.hip
+size_t leaf_moves_lds(int N);
 hipError_t launch_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
                          bool plain, int it, hipStream_t s, int policy_slots = 0);
 int block_tile_waves(const DeviceView &v, int nslots, bool check);
@@ -250,6 +252,10 @@ struct Model {
     double *h_loadrep = nullptr, *h_ru = nullptr;
     int32_t *h_asgrep = nullptr;
     int ru_stride = 0;   // round_upper holds [cap][ru_stride]
+    // the priced moves (nep_leaf_moves; nep_leaf_moves.hip), from their first use on: the pinned staging of a chunk's
+    // [table | fpart] (on the device the table lives in v.share, dead outside an evaluator round)
+    void *pinned_m = nullptr;
+    double *h_table = nullptr, *h_fpart = nullptr;
   };
   std::unique_ptr<LeafWork> leaf;
   // pinned staging of nep_lp_submit's uploads (slots, change offsets / indices / bounds, exact flags): the
@@ -273,6 +279,7 @@ struct Model {
     if (leaf && leaf->pinned) (void)hipHostFree(leaf->pinned);
     if (leaf && leaf->pinned_h) (void)hipHostFree(leaf->pinned_h);
     if (leaf && leaf->pinned_ru) (void)hipHostFree(leaf->pinned_ru);
+    if (leaf && leaf->pinned_m) (void)hipHostFree(leaf->pinned_m);
     for (int k = 0; k < 2; ++k) {
       if (h_sub_i[k]) (void)hipHostFree(h_sub_i[k]);
       if (h_sub_d[k]) (void)hipHostFree(h_sub_d[k]);
@@ -2987,6 +2994,137 @@ int nep_debug_leaf_repair_from(const nep_model_desc *desc, const double *z_leaf,
   std::memcpy(row, pt.row.data(), pt.row.size() * sizeof(int32_t));
   std::memcpy(dst, pt.dst.data(), pt.dst.size() * sizeof(int32_t));
   std::memcpy(val, pt.val.data(), pt.val.size() * sizeof(double));
+  return NEP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// priced moves of a placement (nep_leaf_moves.hip, nep_leaf_moves.cpp; DESIGN.md §7 "Priced moves")
+// ---------------------------------------------------------------------------------------------
+static LeafLimits leaf_limits(const Model &m) {
+  return LeafLimits{m.mem_f.data(), m.capn.data(), m.node_cost.data(), m.node_budget};
+}
+
+static void leaf_moves_out(const std::vector<LeafMove> &mv, int max_moves, int32_t *n_moves, int32_t *kind, int32_t *fn,
+                           int32_t *node, double *delta) {
+  *n_moves = (int32_t)mv.size();
+  for (int q = 0; q < max_moves; ++q) {
+    const bool has = q < (int)mv.size();
+    kind[q] = has ? mv[q].kind : -1;
+    fn[q] = has ? mv[q].fn : -1;
+    node[q] = has ? mv[q].node : -1;
+    delta[q] = has ? mv[q].delta : INF;
+  }
+}
+
+int nep_leaf_moves(void *model, int32_t n, const double *z_leaf, const double *prices, int32_t max_moves,
+                   int32_t *n_moves, int32_t *kind, int32_t *fn, int32_t *node, double *delta, double *lagr,
+                   double *table) {
+  if (!model || !z_leaf || !n_moves) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  if (n < 1) return fail(NEP_ERR_ARG, "n must be at least 1");
+  if (max_moves < 0) return fail(NEP_ERR_ARG, "max_moves must be >= 0");
+  if (max_moves > 0 && (!kind || !fn || !node || !delta)) return fail(NEP_ERR_ARG, "null argument");
+  // the kernel keeps five doubles and four ints per destination / row in LDS and is held to the 64 KiB a launch gets
+  // without asking for more (the evaluator's own 36 bytes fit every admitted N)
+  if (leaf_moves_lds(m.N) > kLeafMovesLdsCap) {
+    int nmax = m.N;
+    while (nmax > 1 && leaf_moves_lds(nmax) > kLeafMovesLdsCap) --nmax;
+    return fail(NEP_ERR_ARG, "nep_leaf_moves: n_nodes " + std::to_string(m.N) + " needs " +
+                                 std::to_string(leaf_moves_lds(m.N)) + " bytes of LDS per workgroup, above " +
+                                 std::to_string(kLeafMovesLdsCap) + " (largest supported n_nodes: " +
+                                 std::to_string(nmax) + ")");
+  }
+  const size_t N = m.N, F = m.F, ni = m.il.n_int;
+  for (size_t k = 0; k < (size_t)n * ni; ++k)
+    if (z_leaf[k] != 0.0 && z_leaf[k] != 1.0)
+      return fail(NEP_ERR_ARG, "placement " + std::to_string(k / ni) + ": entry " + std::to_string(k % ni) +
+                                   " is not 0 or 1 (a leaf fixes every c and n)");
+  for (size_t k = 0; prices && k < (size_t)n * N; ++k)
+    if (!(prices[k] >= 0.0) || prices[k] == INF) return fail(NEP_ERR_ARG, "prices must be finite and >= 0");
+  int rc = ensure_leaf(m);
+  if (rc) return rc;
+  Model::LeafWork &w = *m.leaf;
+  if (!w.pinned_m) {
+    const size_t B = w.cap;
+    if (hipHostMalloc(&w.pinned_m, B * (F * N + F) * sizeof(double)) != hipSuccess) {
+      w.pinned_m = nullptr;
+      return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, priced moves)");
+    }
+    w.h_table = static_cast<double *>(w.pinned_m);
+    w.h_fpart = w.h_table + B * F * N;
+  }
+  const LeafInstance in = leaf_instance(m);
+  const LeafLimits lim = leaf_limits(m);
+  std::vector<uint8_t> c_open(F * N);
+  std::vector<LeafMove> mv;
+  std::vector<int> todo;   // the placements that reach the device
+  for (int b = 0; b < n; ++b) {
+    double nsum = 0.0;
+    leaf_binary(m, z_leaf + b * ni, c_open.data(), &nsum);
+    if (leaf_rejects(m, z_leaf + b * ni, c_open.data())) {
+      mv.clear();
+      leaf_moves_out(mv, max_moves, n_moves + b, kind + (size_t)b * max_moves, fn + (size_t)b * max_moves,
+                     node + (size_t)b * max_moves, delta + (size_t)b * max_moves);
+      if (lagr) lagr[b] = INF;
+      if (table) std::fill(table + b * F * N, table + (b + 1) * F * N, INF);
+    } else {
+      todo.push_back(b);
+    }
+  }
+  for (size_t t0 = 0; t0 < todo.size(); t0 += w.cap) {
+    const int B = (int)std::min<size_t>(w.cap, todo.size() - t0);
+    std::vector<double> nsums(B);
+    for (int q = 0; q < B; ++q) {
+      const int b = todo[t0 + q];
+      leaf_binary(m, z_leaf + b * ni, w.h_open + q * F * N, &nsums[q]);
+      if (prices) std::memcpy(w.h_y + q * N, prices + b * N, N * sizeof(double));
+      else std::fill(w.h_y + q * N, w.h_y + (q + 1) * N, 0.0);
+    }
+    LeafView v = w.v;
+    v.B = B;
+    HIPCHK(hipMemcpyAsync(const_cast<uint8_t *>(v.open), w.h_open, B * F * N, hipMemcpyHostToDevice, m.aux));
+    HIPCHK(hipMemcpyAsync(v.y, w.h_y, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
+    HIPCHK(launch_leaf_moves(v, w.threads, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_table, v.share, B * F * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_fpart, v.fpart, B * F * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipStreamSynchronize(m.aux));
+    for (int q = 0; q < B; ++q) {
+      const int b = todo[t0 + q];
+      const double *tb = w.h_table + q * F * N;
+      if (lagr) {   // L(C, y) = cost_n sum n + the functions' minima - y . cores, as leaf_step sums it per thread
+        double sf = 0.0, sy = 0.0;
+        for (size_t f = 0; f < F; ++f) sf += w.h_fpart[q * F + f];
+        for (size_t j = 0; j < N; ++j) sy += w.h_y[q * N + j] * in.cores[j];
+        lagr[b] = (m.has_n ? m.cost_n * nsums[q] : 0.0) + sf - sy;
+      }
+      if (table) std::memcpy(table + b * F * N, tb, F * N * sizeof(double));
+      mv.clear();
+      if (max_moves > 0) leaf_move_list(in, lim, w.h_open + q * F * N, tb, max_moves, mv);
+      leaf_moves_out(mv, max_moves, n_moves + b, kind + (size_t)b * max_moves, fn + (size_t)b * max_moves,
+                     node + (size_t)b * max_moves, delta + (size_t)b * max_moves);
+    }
+  }
+  return NEP_OK;
+}
+
+int nep_debug_leaf_move_list(const nep_model_desc *desc, const double *z_leaf, const double *table, int32_t max_moves,
+                             int32_t *n_moves, int32_t *kind, int32_t *fn, int32_t *node, double *delta) {
+  if (!desc || !z_leaf || !table || !n_moves) return fail(NEP_ERR_ARG, "null argument");
+  if (max_moves < 0) return fail(NEP_ERR_ARG, "max_moves must be >= 0");
+  if (max_moves > 0 && (!kind || !fn || !node || !delta)) return fail(NEP_ERR_ARG, "null argument");
+  if (desc->device_inputs) return fail(NEP_ERR_ARG, "nep_debug_leaf_move_list takes host arrays (device_inputs = 0)");
+  Model m;
+  int rc = build(m, *desc);
+  if (rc) return rc;
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  std::vector<uint8_t> c_open((size_t)m.F * m.N);
+  double nsum = 0.0;
+  if (!leaf_binary(m, z_leaf, c_open.data(), &nsum)) return fail(NEP_ERR_ARG, "a leaf fixes every c and n at 0 or 1");
+  std::vector<LeafMove> mv;
+  if (!leaf_rejects(m, z_leaf, c_open.data()))
+    leaf_move_list(leaf_instance(m), leaf_limits(m), c_open.data(), table, max_moves, mv);
+  leaf_moves_out(mv, max_moves, n_moves, kind, fn, node, delta);
   return NEP_OK;
 }
 

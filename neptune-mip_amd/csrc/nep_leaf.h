@@ -1,6 +1,7 @@
 // nep_leaf.h — the fixed-placement evaluator (nep_leaf_eval; DESIGN.md §7 "Fixed-placement evaluator"):
 // what its device rounds (nep_leaf.hip), its host repair (nep_leaf_repair.cpp) and the ABI (nep_host.cpp) share.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -96,5 +97,28 @@ struct LeafPoint {
 // load [N] (or nullptr: summed here from asg in row order) are the CPU loads of asg the moves start from
 void leaf_repair(const LeafInstance &in, const uint8_t *c_open, double nsum, const int32_t *asg, LeafPoint &out,
                  const double *load = nullptr);
+
+// Priced moves of a placement (nep_leaf_moves; nep_leaf_moves.hip prices, nep_leaf_moves.cpp composes): table [F][N]
+// holds, per (f, j), the routing part of the change of the Lagrangian bound when a closed placement opens (<= 0) or
+// an open one closes (>= 0, +inf: the function's only destination).
+struct LeafMove {
+  int32_t kind, fn, node;   // NEP_MOVE_ADD / DROP / CLOSE; the function (-1: CLOSE); the node
+  double delta;             // L(C', y) - L(C, y)
+};
+
+// leaf_moves' dynamic LDS (56 (N + 1) + 16 bytes) is held to this: N <= 1169 (nep_leaf_moves refuses a wider model)
+constexpr size_t kLeafMovesLdsCap = 64 * 1024;
+
+// what the move screens need beyond LeafInstance: the evaluator's INFEASIBLE rules on memory and budget
+struct LeafLimits {
+  const double *fmem, *nmem, *cost;   // [F], [N], [N]
+  double budget;
+};
+
+// the moves of the placement c_open [F][N] from its table, screened (an ADD keeps the node's memory and, where it
+// opens the node, the budget; a DROP or CLOSE leaves every function a destination) and in ascending (delta, kind,
+// node, fn) order, at most max_moves of them
+void leaf_move_list(const LeafInstance &in, const LeafLimits &lim, const uint8_t *c_open, const double *table,
+                    int max_moves, std::vector<LeafMove> &out);
 
 }  // namespace nep

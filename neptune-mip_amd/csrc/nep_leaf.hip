@@ -23,16 +23,11 @@
 #include <hip/hip_runtime.h>
 
 #include "nep_leaf.h"
+#include "nep_leaf_device.h"
 
 namespace nep {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_fixed(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // block sum in a fixed order: per-thread strided partials (the caller's), a butterfly per wave, the waves in order
 __device__ __forceinline__ double block_sum_fixed(double v, double *red /* [4] LDS */) {
@@ -67,19 +62,7 @@ __global__ void leaf_assign(LeafView v, int32_t *asg_out) {
   const uint8_t *open = v.open + ((size_t)b * v.F + f) * N;
   const double *y = v.y + (size_t)b * N, *cprf = v.cpr + (size_t)f * N;
   if (tid < 64) {   // the open list, in chunks of 64 destinations
-    int cnt = 0;
-    for (int base = 0; base < N; base += 64) {
-      const int j = base + lane;
-      const bool o = j < N && open[j] != 0;
-      const unsigned long long m = __ballot(o);
-      const int k = cnt + __popcll(m & ((1ull << lane) - 1ull));
-      if (o) {
-        oj[k] = j;
-        yc[k] = y[j] * cprf[j];
-      }
-      if (j < N) kof[j] = o ? k : -1;
-      cnt += __popcll(m);
-    }
+    const int cnt = leaf_open_list(open, y, cprf, N, lane, oj, yc, kof);
     if (lane == 0) *ksh = cnt;
   }
   __syncthreads();
@@ -142,9 +125,7 @@ __global__ void leaf_assign(LeafView v, int32_t *asg_out) {
     share[j] = s * cprf[j];
   }
   if (tid < 64) {
-    double s = 0.0;
-    for (int row = lane; row < nl; row += 64) s += vmin[row];
-    s = wave_sum_fixed(s);
+    const double s = leaf_rows_sum(vmin, nl, lane);
     if (lane == 0) v.fpart[(size_t)b * v.F + f] = s;
   }
 }
