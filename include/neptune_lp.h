@@ -373,6 +373,12 @@ int nep_debug_state(void *model, int32_t slot, double *y, double *kz, float *kty
 /* API 12: per routing row of a slot (length R), the nonzeros its Halpern anchor is held with (17 = dense) and, on a
  * facility-relaxation model, the nonzeros of its x <= c duals (counted on the host) */
 int nep_debug_sparse_rows(void *model, int32_t slot, int32_t *anchor_cnt, float *lambda_nnz);
+/* facility-relaxation model, finished slot (any pointer may be NULL; padding columns dropped): the duals of the rows
+ * x[r, j] - c[f, j] <= 0 as the device holds them, lambda [R][N] — they live outside the dual vector nep_debug_state
+ * reads —, their sums over the routing rows of each function as fac_x_pass left them, lsum [F][N], and the row scale
+ * of those rows, rho_l [F][N] (f32, the value the kernels multiply with).  NEP_ERR_STATE for an iterating slot,
+ * NEP_ERR_ARG for a reference-relaxation model.  Lets the suite compare single iterations with a mirror. */
+int nep_debug_fac_state(void *model, int32_t slot, float *lambda, float *lsum, float *rho_l);
 /* host-only model build (no device work): step size, scalings, row norms, dims = {R, F, n_int,
  * n_dual}.  Lets the CPU test-suite check the model build without a GPU. */
 int nep_debug_build(const nep_model_desc *desc, double *eta, double *rho, double *gam, double *rownorm,

@@ -303,7 +303,8 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_bnb_sync_set", "nep_bnb_export_nodes", "nep_bnb_import_nodes", "nep_lp_get_reduced_costs",
            "nep_lp_rc_fixings", "nep_debug_block_split", "nep_leaf_eval", "nep_leaf_routing_entries",
            "nep_debug_leaf_repair", "nep_bnb_set_leaf_engine", "nep_bnb_get_leaf_stats", "nep_bnb_incumbent_routing",
-           "nep_leaf_eval_ex", "nep_debug_leaf_repair_from", "nep_leaf_moves", "nep_debug_leaf_move_list")
+           "nep_leaf_eval_ex", "nep_debug_leaf_repair_from", "nep_leaf_moves", "nep_debug_leaf_move_list",
+           "nep_debug_fac_state")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -358,6 +359,7 @@ def load_library(path=None):
     lib.nep_reset_stats.restype = None
     lib.nep_lp_get_diag.argtypes = [vp, i32, _dp]
     lib.nep_debug_sparse_rows.argtypes = [vp, i32, vp, vp]
+    lib.nep_debug_fac_state.argtypes = [vp, i32, vp, vp, vp]
     lib.nep_debug_build.argtypes = [ctypes.POINTER(ModelDesc), _dp, _dp, _dp, _dp, ctypes.POINTER(i32)]
     lib.nep_debug_state.argtypes = [vp, i32, _dp, _dp, ctypes.POINTER(ctypes.c_float), _dp, _dp]
     lib.nep_debug_presolve.argtypes = [ctypes.POINTER(ModelDesc), i32, _dp, _dp, pi32, pi32, _dp, _dp]
@@ -984,6 +986,15 @@ class LPModel:
         _check(self._lib, self._lib.nep_debug_state(self._h, int(slot), _ptr(y), _ptr(kz), None, _ptr(lb), _ptr(ub)),
                "nep_debug_state")
         return {"y": y, "kz": kz, "lb": lb, "ub": ub}
+
+    def debug_fac_state(self, slot):
+        """Facility relaxation, finished slot (nep_debug_fac_state): the x <= c duals lam [R, N], their per-function
+        sums lsum [F, N] and the row scale rho_l [F, N] of those rows, float32 as the device holds them."""
+        lam = np.zeros((self.info.n_rows, self.N), np.float32)
+        lsum, rho_l = np.zeros((self.F, self.N), np.float32), np.zeros((self.F, self.N), np.float32)
+        _check(self._lib, self._lib.nep_debug_fac_state(self._h, int(slot), _ptr(lam), _ptr(lsum), _ptr(rho_l)),
+               "nep_debug_fac_state")
+        return {"lam": lam, "lsum": lsum, "rho_l": rho_l}
 
     def set_reference_weight(self, omega_ref):
         """Warm starts take their primal weight in [floor, cap] x omega_ref (nep_lp_set_reference_weight, API 10);

@@ -2603,6 +2603,24 @@ int nep_debug_sparse_rows(void *model, int32_t slot, int32_t *anchor_cnt, float 
   return NEP_OK;
 }
 
+int nep_debug_fac_state(void *model, int32_t slot, float *lambda, float *lsum, float *rho_l) {
+  if (!model) return fail(NEP_ERR_ARG, "null model");
+  Model &m = *static_cast<Model *>(model);
+  if (!m.fac) return fail(NEP_ERR_ARG, "not a facility-relaxation model");
+  if (slot < 0 || slot >= m.max_batch) return fail(NEP_ERR_ARG, "slot out of range");
+  // (the block in flight rewrites lambda and its sums on `stream`; this read runs on the auxiliary stream)
+  if (m.busy[slot]) return fail(NEP_ERR_STATE, "slot is still iterating");
+  const DeviceView &v = m.v;
+  const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
+  const size_t wN = m.N * sizeof(float), wNP = m.NP * sizeof(float);
+  // rows of NP floats on the device, of N on the host: the padding columns stay behind
+  if (lambda) HIPCHK(hipMemcpy2DAsync(lambda, wN, v.lam + (size_t)slot * v.sx, wNP, wN, m.R, d2h, m.aux));
+  if (lsum) HIPCHK(hipMemcpy2DAsync(lsum, wN, v.lsum + (size_t)slot * v.slsum, wNP, wN, m.F, d2h, m.aux));
+  if (rho_l) HIPCHK(hipMemcpy2DAsync(rho_l, wN, v.rho_l, wNP, wN, m.F, d2h, m.aux));
+  HIPCHK(hipStreamSynchronize(m.aux));
+  return NEP_OK;
+}
+
 int nep_debug_build(const nep_model_desc *desc, double *eta, double *rho, double *gam, double *rownorm, int32_t *dims) {
   if (!desc) return fail(NEP_ERR_ARG, "null argument");
   if (desc->device_inputs) return fail(NEP_ERR_ARG, "nep_debug_build takes host arrays (device_inputs = 0)");

@@ -1,5 +1,6 @@
 """Instances, node boxes and the launch-tile rule shared by the kernel-vs-mirror tests (test_gpu_iterates.py, the wide
-read-out cases of test_gpu_aux.py) and their CPU checks (test_abi.py).
+read-out cases of test_gpu_aux.py) and their CPU checks (test_abi.py); at the end of the file the same for the
+facility relaxation (test_gpu_fac_iterates.py, test_ref_fac.py).
 
 Instances (F = 4 functions, N nodes, MinDelayAndUtilization): every number the kernels hold in float32 is exactly
 representable there (integer delays and workloads, core_per_req = k / 1024), so the fp64 mirror and the engine
@@ -178,16 +179,137 @@ def instance(N, step=1, seed=0):
     return d
 
 
-def boxes(N, n_int, step=1):
+def boxes(N, n_int, step=1, n_functions=F):
     """[2, n_int] lower / upper bounds: the root box (no fixing) and the leaf-type box (c = 1 on leaf_open, 0
     elsewhere; everything else free).  Step 2 (delete: sum c may not grow past the two old placements per function)
-    leaves c free on leaf_open instead of forcing it to 1."""
+    leaves c free on leaf_open instead of forcing it to 1.  (n_functions > F: function f opens leaf_open(N, f % F).)"""
     lb = np.full((2, n_int), -np.inf)
     ub = np.full((2, n_int), np.inf)
-    ub[1, :F * N] = 0.0
-    for f in range(F):
-        for j in leaf_open(N, f):
+    ub[1, :n_functions * N] = 0.0
+    for f in range(n_functions):
+        for j in leaf_open(N, f % F):
             ub[1, f * N + j] = 1.0
             if step == 1:
                 lb[1, f * N + j] = 1.0
     return lb, ub
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# facility relaxation (nep_fac.hip; test_gpu_fac_iterates.py and its CPU checks test_ref_fac.py)
+# ---------------------------------------------------------------------------------------------------------------
+FAC_WIDE_F = 67                          # fac_node_pass sums per = ceil(F / 64) = 2 functions per group, last group short
+
+
+def fac_lds_bytes(tw, NP, check):
+    """nep_internal.h fac_lds_bytes."""
+    return ((2 if check else 1) * tw + tw + (tw if check else 0) + 3) * NP * 4 + 3 * NP * 8
+
+
+def fac_max_nodes():
+    """The largest N a facility model admits (nep_internal.h max_padded_width)."""
+    NP = 4
+    while fac_lds_bytes(4, NP + 4, True) <= LDS_CAP:
+        NP += 4
+    return NP
+
+
+def fac_tile_waves(N, nslots, check, n_functions=F):
+    """nep_fac.hip fac_tile_waves: waves per fac_x_pass workgroup."""
+    tw = 4
+    while tw < 16 and nslots * n_functions * tw < 4096:
+        tw *= 2
+    if cpl_of(N) >= 4 and tw > 8:
+        tw = 8
+    while tw > 4 and fac_lds_bytes(tw, padded(N), check) > LDS_CAP:
+        tw //= 2
+    return tw
+
+
+def fac_variants(N, nslots, n_functions=F):
+    """(CPL, TW, pass kind) of the fac_x_pass launches of a cold LP batch of `nslots` slots."""
+    return {(cpl_of(N), fac_tile_waves(N, nslots, kind == "CHECK", n_functions), kind) for kind in KINDS}
+
+
+def fac_dispatchable(function_counts=(F, FAC_WIDE_F)):
+    """Every (CPL, TW, pass kind) the launchers can dispatch for these function counts at some admitted N and slot
+    count."""
+    out = set()
+    for nf in function_counts:
+        for N in range(1, fac_max_nodes() + 1):
+            for ns in (1, 2, 7, 8, 15, 16, 64, 127, 128, 255, 256, 1024):
+                out |= fac_variants(N, ns, nf)
+    return out
+
+
+def fac_matrix():
+    """(N, F, iterating slots, box of a lone slot or None: slots alternate root / leaf) of every engine run of
+    test_gpu_fac_iterates.py."""
+    runs = []
+    for N in EXTRA_CHUNK:
+        for ns in SLOT_COUNTS:
+            runs += [(N, F, ns, box) for box in ((0, 1) if ns == 1 else (None,))]
+    runs += [(N, F, 256, None) for N in (254, 510, 1022, fac_max_nodes() - 2, fac_max_nodes())]
+    runs += [(26, FAC_WIDE_F, 2, None)]
+    return runs
+
+
+def fac_instance(N, n_functions=F, seed=0):
+    """Data of the N-node facility instance: the recipe of instance() (integer delays and workloads, core_per_req =
+    k / 1024: float32 holds the data exactly), but function 0 loads min(37, N - 1) sources plus one pooled row — 38
+    rows from N = 38 on: more than two passes of a 16-wave tile, and no multiple of 4 — and every other function 8
+    sources plus the pooled row: 9 rows, so some waves of a 16-wave tile get none.  R stays near 65 at F = 4.  Leaf
+    nodes (leaf_nodes) have the memory for every function at once."""
+    from core.utils.data import Data
+    nf = n_functions
+    rng = np.random.default_rng(7000 * N + 13 * nf + seed)
+    D = rng.integers(1, 100, size=(N, N))
+    np.fill_diagonal(D, 0)
+    free = np.setdiff1d(np.arange(N), leaf_nodes(N))
+    W = np.zeros((nf, N), np.int64)
+    src0 = np.r_[np.sort(rng.choice(N - 1, size=min(37, N - 1) - 1, replace=False)), N - 1]
+    W[0, src0] = rng.integers(1, 9, size=src0.size)
+    W[0, N - 1] = 8
+    loaded = {}
+    for f in range(1, nf):
+        loaded[f] = np.sort(rng.choice(free, size=min(8, free.size), replace=False))
+        W[f, loaded[f]] = rng.integers(1, 51, size=loaded[f].size)
+    cpr = rng.integers(10, 103, size=(nf, N)) / 1024.0
+    cpr[0, N - 1] = 64 / 1024.0
+    cores = rng.integers(8, 65, size=N) / 64.0
+    node_mem = rng.integers(64, 257, size=N).astype(float)
+    fn_mem = rng.integers(4, 33, size=nf).astype(float)
+    # lambda moves only where a row's reflected flow passes c: in the leaf box (c = 1) where a row sends everything to
+    # one destination.  Function 0's own open node of every chunk index is 100 away from every source but one, which
+    # has it at delay 0, every other node at 99 and workload 50, and so routes there alone within the first block —
+    # in every 256-destination chunk index, the last included
+    special = [int(i) for i in src0 if i in free]                # (sources no leaf box opens as destinations)
+    for q, j in enumerate(chunk_nodes(N, 0)):
+        D[:, j] = 100
+        D[special[q], :] = 99
+        D[special[q], special[q]] = D[special[q], j] = 0
+        W[0, special[q]] = 50
+    for q, j in enumerate(chunk_nodes(N, 1)):
+        D[loaded[1][q], j] = 0
+        W[1, loaded[1][q]] = 50
+        cores[j] = 1.0 / 16
+    cores[N - 1] = 1.0 / 64
+    load = float((W * cpr.max(axis=1, keepdims=True)).sum())
+    for j in (0, 8, 9):
+        cores[j] = float(2 ** np.ceil(np.log2(load)))
+    node_mem[leaf_nodes(N)] = max(256.0, float(2 ** np.ceil(np.log2(fn_mem.sum()))))
+    node_mem[N - 1] = fn_mem.sum()       # the last node holds every function with no memory to spare: whenever the c
+                                         # there run ahead of n, C3 is violated and y3 moves (the last chunk index)
+    d = Data([f"node_{i}" for i in range(N)], [f"ns/fn_{f}" for f in range(nf)])
+    d.node_memory_matrix = node_mem
+    d.function_memory_matrix = fn_mem
+    d.node_delay_matrix = D
+    d.workload_matrix = W
+    d.cores_matrix = cpr
+    d.core_per_req_matrix = cpr
+    d.max_delay_matrix = np.full(nf, 1000)
+    d.response_time_matrix = np.zeros((nf, N), np.int64)
+    d.node_cores_matrix = cores
+    d.old_allocations_matrix = np.ones((nf, N), np.int64)
+    d.node_costs = np.full(N, 5)
+    d.node_budget = 300
+    return d

@@ -39,7 +39,7 @@ Not covered, by construction of these short cold runs: the memory duals y3 and t
 every case, as do (step 2) the score row's dual unless iter_cases.STEP2_KW makes it move; the padding columns
 j >= N of x are not readable through the C ABI (only their effect on the sums is); the pooled / loaded shift, dual
 polishing, warm starts and the full (unreduced) step-2 block are excluded by precondition or not mirrored; the
-facility kernels have no mirror.
+facility kernels have their own mirror and file (ref_fac.py, test_gpu_fac_iterates.py).
 
 Measured on an MI355X (worst snapshot and slot per run; kernel = |kernel - fp64 mirror|; each test prints its own
 table with -s).  Kernel, over all 21 runs: x 5e-9 .. 5.7e-5 (largest at N = 1416), z <= 2.2e-11, y <= 2.1e-10,
