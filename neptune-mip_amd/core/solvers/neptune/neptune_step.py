@@ -5,7 +5,7 @@ Reference classes (same names, constructor keywords and side effects on `Data`):
   NeptuneStep2Base / NeptuneStep2*       `core/solvers/neptune/neptune_step2.py:5-93`
 The reference enumerates the model row by row through pywraplp (`neptune/utils/variables.py`,
 `constraints_step1.py`, `constraints_step2.py`, `objectives.py`) and hands it to SCIP.  Here the
-same model is built structurally by the engine (`nep_model_create`, csrc/nep_host.cpp build(); row
+same model is built structurally by the engine (`nep_model_create`, csrc/nep_model_build.cpp build(); row
 map in DESIGN.md §2) and solved by the batched GPU branch-and-bound (core/engine/bnb.py).
 
 results() returns x[i][f][j] and c[f][j] of the reference's `output_x_and_c`

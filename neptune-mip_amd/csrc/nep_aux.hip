@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "nep_internal.h"
+#include "nep_launch.h"
 
 namespace nep {
 

@@ -33,12 +33,7 @@
 #include <vector>
 
 #include "../../include/neptune_lp.h"
-
-namespace nep {
-int set_error(int code, const char *msg);   // nep_host.cpp: nep_last_error's thread-local message
-bool model_is_facility(void *model);        // nep_host.cpp: the handle is a NEP_RELAX_FACILITY model
-bool model_has_leaf_eval(void *model);      // nep_host.cpp: the handle is a step-1 reference model (nep_leaf_eval)
-}
+#include "nep_internal.h"
 
 namespace {
 

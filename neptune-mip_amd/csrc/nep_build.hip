@@ -1,7 +1,7 @@
 // nep_build.hip — gfx950 kernels of the model build: the step size eta = 0.95 / ||K̃||_2 by power iteration on
 // K̃ᵀK̃ (K̃ = diag(rho) K diag(1, gam): the routing columns keep scale 1) over the model's structured rows, in fp64,
 // on the device (nep_model_create; DESIGN.md §6 "Device build").  The same operator as the host power iteration
-// nep_debug_build keeps (nep_host.cpp power_host), from the same start vector: 60 passes over the R x N routing
+// nep_debug_build keeps (nep_model_build.cpp power_host), from the same start vector: 60 passes over the R x N routing
 // entries took 1.5-6 s of host time per 512x256 model (two thirds of its build), ~10 ms here.
 //
 //   pi_fwd_rows   per function f (one workgroup): column sums S[f, j] of its rows into the C1/C2 rows, the
@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "nep_internal.h"
+#include "nep_launch.h"
 
 namespace nep {
 

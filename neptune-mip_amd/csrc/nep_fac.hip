@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "nep_internal.h"
+#include "nep_launch.h"
 #include "nep_device.h"
 
 namespace nep {

@@ -90,7 +90,7 @@ constexpr int kWave = 64;
 
 // Dynamic LDS of one x-pass workgroup of `tw` waves on rows of NP (padded) destinations, in bytes — the one
 // formula behind the launch size (launch_x_tw / launch_fac_tw), the choice of waves per workgroup (tile_waves /
-// fac_tile_waves) and the widths a model may have (build(), nep_host.cpp).
+// fac_tile_waves) and the widths a model may have (build(), nep_model_build.cpp).
 //   reference relaxation (x_pass): per wave the column-sum and CPU-sum accumulators (fp32; fp64 on certificate
 //   iterations, plus the fp32 reflected sums of a NEP_INLINE_REFLECT build), the packed-dual constants lK / lC, and on
 //   certificate iterations their fp64 copies, the repaired prices and the pooled row's flow (4 x NP doubles)
@@ -286,5 +286,10 @@ struct SlotCopyN {
   int32_t src[kPairs], dst[kPairs];
   int nseg, npairs;
 };
+
+// what the native tree search (nep_bnb.cpp, plain C++) asks of the host runtime (nep_host.cpp)
+int set_error(int code, const char *msg);   // nep_last_error's thread-local message; returns code
+bool model_is_facility(void *model);        // the handle is a NEP_RELAX_FACILITY model
+bool model_has_leaf_eval(void *model);      // the handle is a step-1 reference model (nep_leaf_eval)
 
 }  // namespace nep

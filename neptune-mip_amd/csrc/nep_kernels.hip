@@ -28,6 +28,7 @@
 #include <cmath>
 
 #include "nep_internal.h"
+#include "nep_launch.h"
 #include "nep_device.h"
 
 // (NEP_INLINE_REFLECT, the build flag of the inline reflection: nep_internal.h)
@@ -1675,7 +1676,7 @@ __global__ void node_bounds_base(DeviceView v, const int32_t *__restrict__ slots
   uint8_t *mask = v.mask + slot * v.smask;
   for (int64_t i = tid; i < v.smask; i += stride) mask[i] = bmask[i];
 }
-// ... then the node's packed bound changes (presolve_node, nep_host.cpp), with the destination
+// ... then the node's packed bound changes (presolve_node, nep_presolve.cpp), with the destination
 // masks of the changed c[f, j]
 __global__ void node_bounds_scatter(DeviceView v, const int32_t *__restrict__ slots, const int32_t *__restrict__ off,
                                     const int32_t *__restrict__ idx, const double *__restrict__ cl,
@@ -1733,8 +1734,6 @@ static int tile_waves(const DeviceView &v, int nslots, bool check) {
   return tw;
 }
 
-int fac_block_tile_waves(const DeviceView &v, int nslots, bool check);   // (nep_fac.hip fac_tile_waves)
-
 // waves per x-pass workgroup of a launch over `nslots` slots, plain or certificate variant, either relaxation
 int block_tile_waves(const DeviceView &v, int nslots, bool check) {
   return v.fac ? fac_block_tile_waves(v, nslots, check) : tile_waves(v, nslots, check);
@@ -1765,11 +1764,6 @@ static hipError_t launch_x_cpl(const DeviceView &v, const int32_t *slots, int ns
     default: return hipErrorInvalidValue;
   }
 }
-
-hipError_t launch_fac_x_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
-                             bool plain, int it, hipStream_t s, int policy_slots);
-hipError_t launch_fac_node_pass(const DeviceView &v, const int32_t *slots, int nslots, bool check, bool init, bool first,
-                                bool plain, int it, hipStream_t s);
 
 // policy_slots: the slot count behind the non-temporal policy when the launch covers one slot group of a block
 // (block_split below) — the whole block's, so a group streams as the unsplit launch would; 0: nslots

@@ -1,5 +1,5 @@
 // nep_leaf.h — the fixed-placement evaluator (nep_leaf_eval; DESIGN.md §7 "Fixed-placement evaluator"):
-// what its device rounds (nep_leaf.hip), its host repair (nep_leaf_repair.cpp) and the ABI (nep_host.cpp) share.
+// what its device rounds (nep_leaf.hip), its host repair (nep_leaf_repair.cpp) and the ABI (nep_leaf_host.cpp) share.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -22,6 +22,7 @@
 // threads) and many workgroups share a CU.
 #include <hip/hip_runtime.h>
 
+#include "nep_launch.h"
 #include "nep_leaf.h"
 #include "nep_leaf_device.h"
 
@@ -199,9 +200,6 @@ __global__ void leaf_step(LeafView v, int last) {
     if (move) y[j] = fmax(0.0, yj + theta * g[j]);
   }
 }
-
-hipError_t launch_leaf_heur_init(const LeafView &v, const LeafHeurView &h, hipStream_t s);    // nep_leaf_heur.hip
-hipError_t launch_leaf_repair(const LeafView &v, const LeafHeurView &h, int rd, hipStream_t s);
 
 // the rounds 0 .. rounds of a chunk, back to back on s; `threads`: leaf_assign's workgroup (64, 128 or 256); heur (or
 // nullptr): the per-round repair of nep_leaf_heur.hip, serial in the round between leaf_node and leaf_step

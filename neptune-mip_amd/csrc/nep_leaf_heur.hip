@@ -28,6 +28,7 @@
 
 #include <climits>
 
+#include "nep_launch.h"
 #include "nep_leaf.h"
 
 namespace nep {

@@ -1,0 +1,467 @@
+// nep_leaf_host.cpp — the host side of the fixed-placement evaluator (nep_leaf_eval, nep_leaf_routing_entries,
+// nep_leaf_moves): argument checks, the device workspace, staging of a chunk of placements, the launches
+// of nep_leaf.hip / nep_leaf_heur.hip / nep_leaf_moves.hip and the read-outs through nep_leaf_repair.cpp /
+// nep_leaf_moves.cpp.
+#include "nep_model.h"
+
+using namespace nep;
+
+// ---------------------------------------------------------------------------------------------
+// fixed-placement evaluator (nep_leaf.hip, nep_leaf_repair.cpp)
+// ---------------------------------------------------------------------------------------------
+namespace nep {
+
+const char *const kLeafRefusal =
+    "the fixed-placement evaluator takes step-1 reference-relaxation models (NEP_STEP1, NEP_RELAX_REFERENCE)";
+
+LeafInstance leaf_instance(const Model &m) {
+  LeafInstance in{};
+  in.N = m.N; in.F = m.F; in.R = m.R; in.has_n = m.has_n;
+  in.eps = m.eps; in.kobj = m.kobj; in.cost_n = m.cost_n;
+  in.D = m.Dh.data(); in.W = m.W.data(); in.cpr = m.cprh.data(); in.cores = m.capn.data() + m.N;
+  in.row_f = m.row_f.data(); in.row_src = m.row_src.data(); in.frow = m.frow.data();
+  return in;
+}
+
+// every c and n of z is 0 or 1; c_open [F*N] gets c, *nsum the open nodes
+bool leaf_binary(const Model &m, const double *z, uint8_t *c_open, double *nsum) {
+  const int FN = m.F * m.N;
+  for (int k = 0; k < m.il.n_int; ++k)
+    if (z[k] != 0.0 && z[k] != 1.0) return false;
+  for (int k = 0; k < FN; ++k) c_open[k] = z[m.il.oc + k] != 0.0;
+  double s = 0.0;
+  for (int j = 0; j < m.N && m.has_n; ++j) s += z[m.il.on + j];
+  *nsum = s;
+  return true;
+}
+
+// a row without x rejects the placement: C3 memory, C6/C7 n against c, C8 budget, a function without a destination
+bool leaf_rejects(const Model &m, const double *z, const uint8_t *c_open) {
+  const int N = m.N, F = m.F;
+  for (int j = 0; j < N; ++j) {
+    double mem = 0.0;
+    bool any = false;
+    for (int f = 0; f < F; ++f)
+      if (c_open[(size_t)f * N + j]) { mem += m.mem_f[f]; any = true; }
+    if (mem > m.capn[j] + 1e-9) return true;
+    if (m.has_n) {
+      const double nj = z[m.il.on + j];
+      if (any != (nj != 0.0)) return true;
+      if (m.node_cost[j] * nj > m.node_budget + 1e-9) return true;
+    }
+  }
+  for (int f = 0; f < F; ++f) {
+    bool any = false;
+    for (int j = 0; j < N && !any; ++j) any = c_open[(size_t)f * N + j] != 0;
+    if (!any) return true;
+  }
+  return false;
+}
+
+void leaf_point_out(const LeafPoint &pt, int32_t *row, int32_t *dst, double *val) {
+  std::memcpy(row, pt.row.data(), pt.row.size() * sizeof(int32_t));
+  std::memcpy(dst, pt.dst.data(), pt.dst.size() * sizeof(int32_t));
+  std::memcpy(val, pt.val.data(), pt.val.size() * sizeof(double));
+}
+
+}  // namespace nep
+
+// a failure part-way (rc != 0) gives back what the call allocated since `mark` (the next call starts over); returns rc
+static int leaf_allocs_rollback(Model &m, size_t mark, int rc) {
+  while (rc && m.allocs.size() > mark) {
+    (void)hipFree(m.allocs.back());
+    m.allocs.pop_back();
+  }
+  return rc;
+}
+
+// the evaluator's workspace, on first use: one chunk of `cap` placements (the shares, [cap][F][N] doubles, held to
+// 64 MiB; at most 64 placements), the fp64 instance on the device and the pinned staging of a chunk
+static int ensure_leaf_alloc(Model &m) {
+  std::unique_ptr<Model::LeafWork> w(new Model::LeafWork());
+  const size_t N = m.N, F = m.F, R = m.R;
+  w->cap = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)64 << 20) / (F * N * sizeof(double))));
+  int maxrf = 1;
+  for (int f = 0; f < m.F; ++f) maxrf = std::max(maxrf, m.frow[f + 1] - m.frow[f]);
+  // leaf_assign's workgroup: sized to the rows of a function while every function takes them a lane per row (N <=
+  // kLeafLaneK: no open list is longer); else a function may take a wave per row, and gets all four waves
+  w->threads = m.N > kLeafLaneK ? kLeafThreads : maxrf <= 64 ? 64 : maxrf <= 128 ? 128 : kLeafThreads;
+  const size_t B = w->cap;
+  LeafView &v = w->v;
+  v.N = m.N; v.F = m.F; v.R = m.R; v.B = 0; v.kobj = m.kobj;
+  v.frow = m.v.frow;
+  int rc;
+  std::vector<int32_t> src(m.row_src.begin(), m.row_src.end());
+  std::vector<double> cores(m.capn.begin() + N, m.capn.end());
+  if ((rc = upload(m, &v.row_src, src))) return rc;
+  if ((rc = upload(m, &v.D, m.Dh))) return rc;
+  if ((rc = upload(m, &v.W, m.W))) return rc;
+  if ((rc = upload(m, &v.cpr, m.cprh))) return rc;
+  if ((rc = upload(m, &v.cores, cores))) return rc;
+  uint8_t *d_open = nullptr;
+  if ((rc = dalloc(m, &d_open, B * F * N))) return rc;
+  v.open = d_open;
+  if ((rc = dalloc(m, &v.y, B * N))) return rc;
+  if ((rc = dalloc(m, &v.ybest, B * N))) return rc;
+  if ((rc = dalloc(m, &v.share, B * F * N))) return rc;
+  if ((rc = dalloc(m, &v.fpart, B * F))) return rc;
+  if ((rc = dalloc(m, &v.load, B * N))) return rc;
+  if ((rc = dalloc(m, &v.g, B * N))) return rc;
+  if ((rc = dalloc(m, &v.asg0, B * R))) return rc;
+  if ((rc = dalloc(m, &v.asg, B * R))) return rc;
+  if ((rc = dalloc(m, &v.ctrl, B))) return rc;
+  // pinned: [ctrl | y | load | asg0 | open]
+  const size_t bytes = B * (sizeof(LeafCtrl) + 2 * N * sizeof(double) + R * sizeof(int32_t) + F * N) + 64;
+  if (hipHostMalloc(&w->pinned, bytes) != hipSuccess) return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator)");
+  char *p = static_cast<char *>(w->pinned);
+  w->h_ctrl = reinterpret_cast<LeafCtrl *>(p); p += B * sizeof(LeafCtrl);
+  w->h_y = reinterpret_cast<double *>(p); p += B * N * sizeof(double);
+  w->h_load = reinterpret_cast<double *>(p); p += B * N * sizeof(double);
+  w->h_asg0 = reinterpret_cast<int32_t *>(p); p += B * R * sizeof(int32_t);
+  w->h_open = reinterpret_cast<uint8_t *>(p);
+  m.leaf = std::move(w);
+  return NEP_OK;
+}
+static int ensure_leaf(Model &m) {
+  if (m.leaf) return NEP_OK;
+  const size_t n0 = m.allocs.size();
+  return leaf_allocs_rollback(m, n0, ensure_leaf_alloc(m));
+}
+
+// the per-round repair's workspace (nep_leaf_heur.hip), on the first call that asks for it: the open lists, the
+// repair's state and the best round's copies for one chunk, and round_upper for `rounds` rounds
+static int ensure_leaf_heur(Model &m, int rounds) {
+  Model::LeafWork &w = *m.leaf;
+  const size_t N = m.N, F = m.F, R = m.R, B = w.cap;
+  if (!w.heur) {
+    const size_t n0 = m.allocs.size();
+    LeafHeurView h{};
+    std::vector<int32_t> rf(m.row_f.begin(), m.row_f.end());
+    int rc = upload(m, &h.row_f, rf);
+    if (!rc) rc = dalloc(m, &h.opl, B * F * N);
+    if (!rc) rc = dalloc(m, &h.opn, B * F);
+    if (!rc) rc = dalloc(m, &h.flow, B * R);
+    if (!rc) rc = dalloc(m, &h.room, B * F);
+    if (!rc) rc = dalloc(m, &h.fcost, B * F);
+    if (!rc) rc = dalloc(m, &h.nrows, B * R);
+    if (!rc) rc = dalloc(m, &h.asgrep, B * R);
+    if (!rc) rc = dalloc(m, &h.loadrep, B * N);
+    if (!rc) rc = dalloc(m, &h.best, B);
+    // pinned: [best | loadrep | asgrep]
+    void *pin = nullptr;
+    if (!rc && hipHostMalloc(&pin, B * (sizeof(LeafHeurBest) + N * sizeof(double) + R * sizeof(int32_t)) + 64) !=
+                   hipSuccess)
+      rc = fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, per-round repair)");
+    if (rc) return leaf_allocs_rollback(m, n0, rc);
+    h.floor_ = 1.0 - m.eps;
+    w.hv = h;
+    w.pinned_h = pin;
+    char *p = static_cast<char *>(pin);
+    w.h_best = reinterpret_cast<LeafHeurBest *>(p); p += B * sizeof(LeafHeurBest);
+    w.h_loadrep = reinterpret_cast<double *>(p); p += B * N * sizeof(double);
+    w.h_asgrep = reinterpret_cast<int32_t *>(p);
+    w.heur = true;
+  }
+  if (rounds + 1 > w.ru_stride) {
+    double *d = nullptr;
+    void *pin = nullptr;
+    const int rc = dalloc(m, &d, B * (size_t)(rounds + 1));
+    if (rc) return rc;
+    if (hipHostMalloc(&pin, B * (size_t)(rounds + 1) * sizeof(double)) != hipSuccess)
+      return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, round_upper)");
+    if (w.pinned_ru) (void)hipHostFree(w.pinned_ru);
+    w.pinned_ru = pin;
+    w.h_ru = static_cast<double *>(pin);
+    w.hv.round_upper = d;   // (an earlier, shorter one stays with the model's allocations)
+    w.ru_stride = rounds + 1;
+  }
+  return NEP_OK;
+}
+
+// The argument checks nep_leaf_eval_ex and nep_leaf_moves share, in the order both make them: the model's kind, n, the
+// entry's own checks (own_checks, between the two), every entry of z_leaf 0 or 1, every price finite and >= 0
+// (prices_name: the argument's name in the message).
+template <typename OwnChecks>
+static int leaf_check_args(const Model &m, int32_t n, const double *z_leaf, const double *prices,
+                           const char *prices_name, OwnChecks own_checks) {
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  if (n < 1) return fail(NEP_ERR_ARG, "n must be at least 1");
+  if (const int rc = own_checks()) return rc;
+  const size_t N = m.N, ni = m.il.n_int;
+  for (size_t k = 0; k < (size_t)n * ni; ++k)
+    if (z_leaf[k] != 0.0 && z_leaf[k] != 1.0)
+      return fail(NEP_ERR_ARG, "placement " + std::to_string(k / ni) + ": entry " + std::to_string(k % ni) +
+                                   " is not 0 or 1 (a leaf fixes every c and n)");
+  for (size_t k = 0; prices && k < (size_t)n * N; ++k)
+    if (!(prices[k] >= 0.0) || prices[k] == INF)
+      return fail(NEP_ERR_ARG, std::string(prices_name) + " must be finite and >= 0");
+  return NEP_OK;
+}
+
+// The first pass over a call's placements: those no row without x rejects reach the device, in order; for a rejected
+// one the caller writes its outputs (rejected(b)).
+template <typename Rejected>
+static std::vector<int> leaf_first_pass(const Model &m, int32_t n, const double *z_leaf, Rejected rejected) {
+  const size_t ni = m.il.n_int;
+  std::vector<uint8_t> c_open((size_t)m.F * m.N);
+  std::vector<int> todo;
+  for (int b = 0; b < n; ++b) {
+    double nsum = 0.0;
+    leaf_binary(m, z_leaf + b * ni, c_open.data(), &nsum);
+    if (leaf_rejects(m, z_leaf + b * ni, c_open.data())) rejected(b);
+    else todo.push_back(b);
+  }
+  return todo;
+}
+
+// One chunk of B placements, todo[0 .. B), staged and on its way to the device: their c in h_open, their open nodes in
+// nsums, their prices (or zeros) in h_y; the copies of open and y are enqueued on the auxiliary stream.
+static int leaf_stage_chunk(Model &m, const LeafView &v, const int *todo, int B, const double *z_leaf,
+                            const double *prices, std::vector<double> &nsums) {
+  Model::LeafWork &w = *m.leaf;
+  const size_t N = m.N, F = m.F, ni = m.il.n_int;
+  nsums.resize(B);
+  for (int q = 0; q < B; ++q) {
+    const int b = todo[q];
+    leaf_binary(m, z_leaf + b * ni, w.h_open + q * F * N, &nsums[q]);
+    if (prices) std::memcpy(w.h_y + q * N, prices + b * N, N * sizeof(double));
+    else std::fill(w.h_y + q * N, w.h_y + (q + 1) * N, 0.0);
+  }
+  HIPCHK(hipMemcpyAsync(const_cast<uint8_t *>(v.open), w.h_open, B * F * N, hipMemcpyHostToDevice, m.aux));
+  HIPCHK(hipMemcpyAsync(v.y, w.h_y, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
+  return NEP_OK;
+}
+
+extern "C" {
+
+int nep_leaf_eval(void *model, int32_t n, const double *z_leaf, const nep_leaf_opts *opts, const double *prices_in,
+                  double *lower, double *upper, int32_t *status, double *prices_out, double *cpu) {
+  return nep_leaf_eval_ex(model, n, z_leaf, opts, nullptr, prices_in, lower, upper, status, prices_out, cpu, nullptr,
+                          nullptr, nullptr);
+}
+
+int nep_leaf_eval_ex(void *model, int32_t n, const double *z_leaf, const nep_leaf_opts *opts,
+                     const nep_leaf_heur_opts *heur, const double *prices_in, double *lower, double *upper,
+                     int32_t *status, double *prices_out, double *cpu, int32_t *upper_round, double *device_upper,
+                     double *round_upper) {
+  if (!model || !z_leaf || !lower || !upper || !status) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  const int every = heur ? heur->repair_every : 0;
+  const int rounds = opts ? opts->rounds : 32;
+  const double cutoff = opts ? opts->cutoff : INF;
+  const double tol = opts && opts->tol > 0.0 ? opts->tol : 1e-6;
+  int rc = leaf_check_args(m, n, z_leaf, prices_in, "prices_in", [&]() -> int {
+    if (every < 0) return fail(NEP_ERR_ARG, "repair_every must be >= 0");
+    if (rounds < 0 || cutoff != cutoff) return fail(NEP_ERR_ARG, "bad rounds or cutoff");
+    return NEP_OK;
+  });
+  if (rc) return rc;
+  const size_t N = m.N, F = m.F, R = m.R;
+  if ((rc = ensure_leaf(m))) return rc;
+  if (every && (rc = ensure_leaf_heur(m, rounds))) return rc;
+  Model::LeafWork &w = *m.leaf;
+  w.points.assign(n, LeafPoint());
+  const LeafInstance in = leaf_instance(m);
+  const size_t nr = (size_t)rounds + 1;
+  for (int b = 0; b < n; ++b) {
+    if (upper_round) upper_round[b] = -1;
+    if (device_upper) device_upper[b] = INF;
+    if (round_upper) std::fill(round_upper + b * nr, round_upper + (b + 1) * nr, INF);
+    if (prices_out) std::fill(prices_out + b * N, prices_out + (b + 1) * N, 0.0);
+    if (cpu) std::fill(cpu + b * N, cpu + (b + 1) * N, 0.0);
+  }
+  // the placements that reach the device
+  const std::vector<int> todo = leaf_first_pass(m, n, z_leaf, [&](int b) {
+    lower[b] = upper[b] = INF;
+    status[b] = NEP_LEAF_INFEASIBLE;
+  });
+  std::vector<double> nsums;
+  for (size_t t0 = 0; t0 < todo.size(); t0 += w.cap) {
+    const int B = (int)std::min<size_t>(w.cap, todo.size() - t0);
+    LeafView v = w.v;
+    v.B = B;
+    if ((rc = leaf_stage_chunk(m, v, todo.data() + t0, B, z_leaf, prices_in, nsums))) return rc;
+    for (int q = 0; q < B; ++q) {
+      LeafCtrl &c = w.h_ctrl[q];
+      c = LeafCtrl{};
+      c.base = m.has_n ? m.cost_n * nsums[q] : 0.0;
+      c.best = -INF;
+      c.lam = 1.0;
+      c.cutoff = cutoff;
+    }
+    HIPCHK(hipMemcpyAsync(v.ctrl, w.h_ctrl, B * sizeof(LeafCtrl), hipMemcpyHostToDevice, m.aux));
+    HIPCHK(hipMemcpyAsync(v.ybest, w.h_y, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
+    LeafHeurView hv = w.hv;
+    hv.rounds = rounds;
+    hv.every = every;
+    HIPCHK(launch_leaf_rounds(v, rounds, w.threads, m.aux, every ? &hv : nullptr));
+    // one read at the end: bounds and flags, the best prices, the last loads, the round-0 assignment
+    HIPCHK(hipMemcpyAsync(w.h_ctrl, v.ctrl, B * sizeof(LeafCtrl), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_y, v.ybest, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_load, v.load, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_asg0, v.asg0, B * R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+    if (every) {   // the best repaired round: its objective and number, its loads and assignment; the rounds' verdicts
+      HIPCHK(hipMemcpyAsync(w.h_best, hv.best, B * sizeof(LeafHeurBest), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_loadrep, hv.loadrep, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_asgrep, hv.asgrep, B * R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_ru, hv.round_upper, B * nr * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    }
+    HIPCHK(hipStreamSynchronize(m.aux));
+    for (int q = 0; q < B; ++q) {
+      const int b = todo[t0 + q];
+      const LeafCtrl &c = w.h_ctrl[q];
+      if (every) {
+        if (device_upper) device_upper[b] = w.h_best[q].obj;
+        if (round_upper) std::memcpy(round_upper + b * nr, w.h_ru + q * nr, nr * sizeof(double));
+      }
+      lower[b] = c.best;
+      upper[b] = INF;
+      if (prices_out) std::memcpy(prices_out + b * N, w.h_y + q * N, N * sizeof(double));
+      if (cpu) std::memcpy(cpu + b * N, w.h_load + q * N, N * sizeof(double));
+      if (c.cut) {
+        status[b] = NEP_LEAF_CUTOFF;
+        continue;
+      }
+      LeafPoint &pt = w.points[b];
+      leaf_repair(in, w.h_open + q * F * N, nsums[q], w.h_asg0 + q * R, pt);
+      int from = pt.found ? 0 : -1;
+      if (every && w.h_best[q].round >= 0) {
+        // the device chose the round; its point is the host's, verified in fp64, from the loads the device started at
+        LeafPoint alt;
+        leaf_repair(in, w.h_open + q * F * N, nsums[q], w.h_asgrep + q * R, alt, w.h_loadrep + q * N);
+        if (alt.found && (!pt.found || alt.obj < pt.obj)) {
+          pt = std::move(alt);
+          from = w.h_best[q].round;
+        }
+      }
+      if (upper_round) upper_round[b] = from;
+      if (!pt.found) {
+        status[b] = NEP_LEAF_NO_POINT;
+        continue;
+      }
+      upper[b] = pt.obj;
+      if (cpu) std::memcpy(cpu + b * N, pt.cpu.data(), N * sizeof(double));
+      status[b] = pt.obj - c.best <= tol * std::max(1.0, std::fabs(c.best)) ? NEP_LEAF_EXACT : NEP_LEAF_FEASIBLE;
+    }
+  }
+  return NEP_OK;
+}
+
+int nep_leaf_routing_entries(void *model, int32_t k, int64_t capacity, int64_t *n_entries, int32_t *row, int32_t *dst,
+                             double *val) {
+  if (!model || !n_entries) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  if (!m.leaf || k < 0 || (size_t)k >= m.leaf->points.size())
+    return fail(NEP_ERR_ARG, "no placement " + std::to_string(k) + " in the last nep_leaf_eval call");
+  const LeafPoint &pt = m.leaf->points[k];
+  if (!pt.found) return fail(NEP_ERR_STATE, "placement " + std::to_string(k) + " has no routing (upper = +inf)");
+  const int64_t cnt = (int64_t)pt.row.size();
+  *n_entries = cnt;
+  if (capacity < cnt) return NEP_OK;   // size query
+  if (!row || !dst || !val) return fail(NEP_ERR_ARG, "null argument");
+  leaf_point_out(pt, row, dst, val);
+  return NEP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// priced moves of a placement (nep_leaf_moves.hip, nep_leaf_moves.cpp; DESIGN.md §7 "Priced moves")
+// ---------------------------------------------------------------------------------------------
+namespace nep {
+
+LeafLimits leaf_limits(const Model &m) {
+  return LeafLimits{m.mem_f.data(), m.capn.data(), m.node_cost.data(), m.node_budget};
+}
+
+void leaf_moves_out(const std::vector<LeafMove> &mv, int max_moves, int32_t *n_moves, int32_t *kind, int32_t *fn,
+                    int32_t *node, double *delta) {
+  *n_moves = (int32_t)mv.size();
+  for (int q = 0; q < max_moves; ++q) {
+    const bool has = q < (int)mv.size();
+    kind[q] = has ? mv[q].kind : -1;
+    fn[q] = has ? mv[q].fn : -1;
+    node[q] = has ? mv[q].node : -1;
+    delta[q] = has ? mv[q].delta : INF;
+  }
+}
+
+}  // namespace nep
+
+extern "C" {
+
+int nep_leaf_moves(void *model, int32_t n, const double *z_leaf, const double *prices, int32_t max_moves,
+                   int32_t *n_moves, int32_t *kind, int32_t *fn, int32_t *node, double *delta, double *lagr,
+                   double *table) {
+  if (!model || !z_leaf || !n_moves) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  int rc = leaf_check_args(m, n, z_leaf, prices, "prices", [&]() -> int {
+    if (max_moves < 0) return fail(NEP_ERR_ARG, "max_moves must be >= 0");
+    if (max_moves > 0 && (!kind || !fn || !node || !delta)) return fail(NEP_ERR_ARG, "null argument");
+    // the kernel keeps five doubles and four ints per destination / row in LDS and is held to the 64 KiB a launch
+    // gets without asking for more (the evaluator's own 36 bytes fit every admitted N)
+    if (leaf_moves_lds(m.N) > kLeafMovesLdsCap) {
+      int nmax = m.N;
+      while (nmax > 1 && leaf_moves_lds(nmax) > kLeafMovesLdsCap) --nmax;
+      return fail(NEP_ERR_ARG, "nep_leaf_moves: n_nodes " + std::to_string(m.N) + " needs " +
+                                   std::to_string(leaf_moves_lds(m.N)) + " bytes of LDS per workgroup, above " +
+                                   std::to_string(kLeafMovesLdsCap) + " (largest supported n_nodes: " +
+                                   std::to_string(nmax) + ")");
+    }
+    return NEP_OK;
+  });
+  if (rc) return rc;
+  const size_t N = m.N, F = m.F;
+  if ((rc = ensure_leaf(m))) return rc;
+  Model::LeafWork &w = *m.leaf;
+  if (!w.pinned_m) {
+    const size_t B = w.cap;
+    if (hipHostMalloc(&w.pinned_m, B * (F * N + F) * sizeof(double)) != hipSuccess) {
+      w.pinned_m = nullptr;
+      return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, priced moves)");
+    }
+    w.h_table = static_cast<double *>(w.pinned_m);
+    w.h_fpart = w.h_table + B * F * N;
+  }
+  const LeafInstance in = leaf_instance(m);
+  const LeafLimits lim = leaf_limits(m);
+  std::vector<LeafMove> mv;
+  // the placements that reach the device
+  const std::vector<int> todo = leaf_first_pass(m, n, z_leaf, [&](int b) {
+    mv.clear();
+    leaf_moves_out(mv, max_moves, n_moves + b, kind + (size_t)b * max_moves, fn + (size_t)b * max_moves,
+                   node + (size_t)b * max_moves, delta + (size_t)b * max_moves);
+    if (lagr) lagr[b] = INF;
+    if (table) std::fill(table + b * F * N, table + (b + 1) * F * N, INF);
+  });
+  std::vector<double> nsums;
+  for (size_t t0 = 0; t0 < todo.size(); t0 += w.cap) {
+    const int B = (int)std::min<size_t>(w.cap, todo.size() - t0);
+    LeafView v = w.v;
+    v.B = B;
+    if ((rc = leaf_stage_chunk(m, v, todo.data() + t0, B, z_leaf, prices, nsums))) return rc;
+    HIPCHK(launch_leaf_moves(v, w.threads, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_table, v.share, B * F * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_fpart, v.fpart, B * F * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipStreamSynchronize(m.aux));
+    for (int q = 0; q < B; ++q) {
+      const int b = todo[t0 + q];
+      const double *tb = w.h_table + q * F * N;
+      if (lagr) {   // L(C, y) = cost_n sum n + the functions' minima - y . cores, as leaf_step sums it per thread
+        double sf = 0.0, sy = 0.0;
+        for (size_t f = 0; f < F; ++f) sf += w.h_fpart[q * F + f];
+        for (size_t j = 0; j < N; ++j) sy += w.h_y[q * N + j] * in.cores[j];
+        lagr[b] = (m.has_n ? m.cost_n * nsums[q] : 0.0) + sf - sy;
+      }
+      if (table) std::memcpy(table + b * F * N, tb, F * N * sizeof(double));
+      mv.clear();
+      if (max_moves > 0) leaf_move_list(in, lim, w.h_open + q * F * N, tb, max_moves, mv);
+      leaf_moves_out(mv, max_moves, n_moves + b, kind + (size_t)b * max_moves, fn + (size_t)b * max_moves,
+                     node + (size_t)b * max_moves, delta + (size_t)b * max_moves);
+    }
+  }
+  return NEP_OK;
+}
+
+}  // extern "C"

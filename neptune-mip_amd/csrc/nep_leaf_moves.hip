@@ -19,6 +19,7 @@
 // of LeafCtrl is read or written.
 #include <hip/hip_runtime.h>
 
+#include "nep_launch.h"
 #include "nep_leaf.h"
 #include "nep_leaf_device.h"
 

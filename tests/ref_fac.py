@@ -53,7 +53,7 @@ class RefFac:
             rho_l = 1.0 / np.sqrt(1.0 + self.gam[:FN].reshape(F, N))
         self.rho_l = np.asarray(rho_l, float).reshape(F, N)
         self._eta = None
-        # initial primal weight ||cost~|| / ||b~|| as nep_host.cpp build (C3 / C5 count their capacities)
+        # initial primal weight ||cost~|| / ||b~|| as nep_model_build.cpp build (C3 / C5 count their capacities)
         cn2 = (b.row_m[:, None] * self.cost_x ** 2).sum() + ((self.gam * self.cost_int) ** 2).sum()
         bn2 = ((self.rho[:N] * self.Mem) ** 2).sum() + ((self.rho[N:2 * N] * self.cores) ** 2).sum()
         self.omega0 = float(np.sqrt(cn2 / bn2)) if cn2 > 0 and bn2 > 0 else 1.0

@@ -190,7 +190,7 @@ class RefModel:
         rn = np.where(np.isfinite(hi), np.maximum(rn, np.abs(np.where(np.isfinite(hi), hi, 0))), rn)
         np.maximum.at(rn, self.Kr, np.abs(self.Kv))
         self.rownorm = rn
-        # step 2, reduced disruption block (nep_host.cpp build): mf / mt / a / d follow from c, the
+        # step 2, reduced disruption block (nep_model_build.cpp build): mf / mt / a / d follow from c, the
         # iteration runs on K without D1/D2/D3a/D3b and with D4 as the row sum c (coefficient 1 on every c)
         self.old = old
         self.dred = bool(self.step2 and np.isin(old, (0.0, 1.0)).all()) if dred is None else bool(dred and self.step2)
@@ -226,9 +226,9 @@ class RefModel:
         self.rho, self.gam = rho, gam
         self.sigma_max = self._power()
         self.eta = 0.95 / self.sigma_max
-        # initial primal weight ||c~|| / ||b~|| (scaled space), as nep_host.cpp build()
+        # initial primal weight ||c~|| / ||b~|| (scaled space), as nep_model_build.cpp build()
         cx = self.row_wobj[:, None] * np.where(self.row_src[:, None] >= 0, D[np.maximum(self.row_src, 0)], 0.0)
-        # (reduced step 2: the reduced LP's costs and row bounds at natural bounds, as nep_host.cpp build)
+        # (reduced step 2: the reduced LP's costs and row bounds at natural bounds, as nep_model_build.cpp build)
         ci = self.cost_int
         if self.dred:
             ci, _, self.lo[self.oD4], self.hi[self.oD4] = self.dred_terms(self.nat_lb, self.nat_ub)

@@ -116,7 +116,7 @@ def test_node_presolve_incremental_equals_full(name, k):
 
 def test_parallel_node_presolve_equals_full():
     """Above ~8k integer variables nep_lp_submit presolves a batch's nodes on several host threads
-    (nep_host.cpp presolve_batch; rounding leaves fix every c and n and take the dense row re-test): each
+    (nep_presolve.cpp presolve_batch; rounding leaves fix every c and n and take the dense row re-test): each
     node must still decide feasibility and produce the box the from-scratch presolve does."""
     from core.engine.heuristics import capacity_greedy
     from core.engine.lp import debug_build, debug_presolve
@@ -301,7 +301,7 @@ def test_facility_relaxation_build():
 
 
 def test_presolve_cpu_cover_proves_overloaded_leaf_infeasible():
-    """The node presolve's CPU cover test (nep_host.cpp cpu_cover_ok): testpy's step-1 rounding leaf that opens
+    """The node presolve's CPU cover test (nep_presolve.cpp cpu_cover_ok): testpy's step-1 rounding leaf that opens
     node 0 only (c[0,0] = c[1,0] = n[0] = 1, everything else 0) overloads node 0's CPU — HiGHS finds the box
     infeasible (tools/probes/leaf_limit_probe.py) and PDHG could only stall on it (round-4 GPU suite: testpy's step 1
     ended LIMIT).  Both the from-scratch and the sparse-change presolve must reject it, and the leaf that

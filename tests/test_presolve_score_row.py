@@ -1,4 +1,4 @@
-"""Node presolve of the step-2 score / delay row (csrc/nep_host.cpp score_row_xmin; DESIGN.md §4
+"""Node presolve of the step-2 score / delay row (csrc/nep_presolve.cpp score_row_xmin; DESIGN.md §4
 "Infeasibility"): a node box whose closed placements push the row's smallest activity over the routing
 simplexes above its right-hand side is infeasible.  Checked on every node box a branch-and-bound visits
 on the reference's own step-2 models (the B&B runs on the oracle's HiGHS LPs, tests/oracle_lp.py):
