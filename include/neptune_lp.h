@@ -343,6 +343,37 @@ int nep_leaf_moves(void *model, int32_t n, const double *z_leaf /* [n][n_int] */
 int nep_debug_leaf_move_list(const nep_model_desc *desc, const double *z_leaf, const double *table /* [F][N] */,
                              int32_t max_moves, int32_t *n_moves, int32_t *kind, int32_t *fn, int32_t *node, double *delta);
 
+/* Priced swaps of fixed placements (csrc/nep_leaf_swaps.hip, csrc/nep_leaf_swaps.cpp; DESIGN.md §7 "Priced swaps"): the
+ * exact change of L(C, y) when function f leaves an open destination j for a closed one j', priced jointly — rows of j
+ * fall back to the cheaper of their second choice and j' — for every (f, j, j') of each placement at once.  With bucket
+ * k the loaded rows of f whose minimum is at the k-th open destination oj[k], in ascending row order:
+ *   A_k(j') = sum_{r in bucket k} (min(m1_r, rho_r(j')) - m1_r),  S_k(j') = sum_{r in bucket k} (min(m2_r, rho_r(j')) - m1_r)
+ *   delta(f, oj[k] -> j') = (sum_k A_k + ((S_k - A_k) - cost_n [node oj[k] holds only this placement]))
+ *                           + cost_n [node j' holds none]                     (the cost_n terms: variants with n)
+ * finite even for a function with one destination.  j' must pass NEP_MOVE_ADD's screens (memory, and the budget where
+ * the node opens).  Per (f, j') the source is the k of the smallest delta (ties to the lowest k); per function the
+ * device keeps the per_fn (1 .. 8) cheapest (delta, j'), so per_fn records per (placement, function) are read back
+ * and no [F][N] array crosses to the host unless best / best_from ask for one:
+ *   best [n][F][N]       the cheapest swap of f into j' (+inf: j' open for f, or screened)
+ *   best_from [n][F][N]  its source node (-1: none)
+ * The kept swaps are returned in ascending (delta, fn, to, from) order, at most max_moves per placement (n_moves [n]
+ * of them; the rest of fn / from / to is -1, of delta +inf); the move kind of a swap is NEP_MOVE_SWAP.  Applying one
+ * (clear c[fn, from], and n of that node with its column; set c[fn, to] and n of that node) gives a placement that
+ * passes the INFEASIBLE rules, with L(C', y) = L(C, y) + delta up to fp64 rounding.  lagr, rejected placements
+ * (n_moves = 0, lagr = +inf, best +inf, best_from -1), max_moves = 0, the stream and the refusals are nep_leaf_moves';
+ * per_fn outside 1 .. 8 is NEP_ERR_ARG too. */
+enum { NEP_MOVE_SWAP = 3 };
+int nep_leaf_swaps(void *model, int32_t n, const double *z_leaf /* [n][n_int] */,
+                   const double *prices /* [n][N] >= 0, or NULL: zeros */, int32_t per_fn /* 1..8 */, int32_t max_moves,
+                   int32_t *n_moves /* [n] */, int32_t *fn, int32_t *from, int32_t *to, double *delta /* [n][max_moves] */,
+                   double *lagr /* [n] or NULL */, double *best /* [n][F][N] or NULL */,
+                   int32_t *best_from /* [n][F][N] or NULL */);
+/* host-only: the selection (per_fn cheapest per function) and merge of one placement from given tables, so the CPU
+ * suite checks them without a GPU */
+int nep_debug_leaf_swap_list(int32_t F, int32_t N, const double *best, const int32_t *best_from, int32_t per_fn,
+                             int32_t max_moves, int32_t *n_moves, int32_t *fn, int32_t *from, int32_t *to,
+                             double *delta);
+
 /* The reference's offline scorers and feasibility checkers on a slot's solution, on the device
  * (efttc/utils/objectives.py:23-98, efttc/utils/constraints_step1.py:5-133; booleans are the
  * reference's truthiness, value != 0).  out[NEP_SC_COUNT]: */

@@ -109,10 +109,11 @@ def capacity_greedy(W, D, cpr, cores, fmem, nmem, n_rank, flow=None, start=None,
     return out
 
 
-def apply_move(z, F, N, has_n, kind, fn, node):
-    """z' = the placement z (c f-major [F N], then n [N] where the variant has n) after one priced move (nep_leaf_moves):
-    ADD (0) opens (fn, node) and the node; DROP (1) closes (fn, node), and the node with its last placement; CLOSE (2)
-    closes the node and every placement on it."""
+def apply_move(z, F, N, has_n, kind, fn, node, src=None):
+    """z' = the placement z (c f-major [F N], then n [N] where the variant has n) after one priced move (nep_leaf_moves,
+    nep_leaf_swaps): ADD (0) opens (fn, node) and the node; DROP (1) closes (fn, node), and the node with its last
+    placement; CLOSE (2) closes the node and every placement on it; SWAP (3) moves fn from the node `src` to `node`:
+    closes (fn, src), and that node with its last placement, and opens (fn, node) and the node."""
     z = np.array(z, np.float64, copy=True)
     C = z[:F * N].reshape(F, N)
     kind, fn, node = int(kind), int(fn), int(node)
@@ -125,6 +126,14 @@ def apply_move(z, F, N, has_n, kind, fn, node):
     elif kind == 2:
         C[:, node] = 0.0
         opened = 0.0
+    elif kind == 3:
+        if src is None:
+            raise ValueError("a swap needs its source node")
+        C[fn, int(src)] = 0.0
+        C[fn, node] = 1.0
+        opened = 1.0
+        if has_n:
+            z[F * N + int(src)] = 1.0 if C[:, int(src)].any() else 0.0
     else:
         raise ValueError(f"unknown move kind {kind}")
     if has_n:
@@ -133,15 +142,18 @@ def apply_move(z, F, N, has_n, kind, fn, node):
 
 
 def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_passes=32, time_limit=None, warm=True,
-                     log=None):
+                     log=None, swaps=0, per_fn=4):
     """Local search over placements from z0 [n_int] with the fixed-placement evaluator and its priced moves (DESIGN.md
     §7 "Priced moves").  model: anything with F, N, n_int and leaf_eval / leaf_moves / leaf_routing (LPModel's
     contracts).  Per pass: the moves of the current placement at its evaluated prices, the first `width` applied, the
     neighbours evaluated in one leaf_eval call cut off at the incumbent's upper (from the current prices when `warm`),
     the best accepted when it improves upper by more than 1e-9 max(1, |upper|) (ties: the earlier move); a start
     without a point takes the first neighbour that has one.  Stops at the first pass without an acceptance, at
-    max_passes or at time_limit seconds.  Deterministic.  Returns dict(z, upper, lower, row, dst, val (the routing
-    of z, None without a point), start_upper, passes, evaluated, accepted [(kind, fn, node, delta, upper)])."""
+    max_passes or at time_limit seconds.  swaps > 0 (the model then has leaf_swaps too): each pass also asks for that
+    many priced swaps (nep_leaf_swaps, the per_fn cheapest destinations per function) at the same prices; their
+    neighbours follow the single moves' in the same leaf_eval call.  Deterministic.  Returns dict(z, upper, lower, row,
+    dst, val (the routing of z, None without a point), start_upper, passes, evaluated, accepted [(kind, fn, node,
+    delta, upper), and for a swap (3, fn, to, delta, upper, from)])."""
     import time
     F, N = int(model.F), int(model.N)
     has_n = int(model.n_int) == F * N + N
@@ -157,11 +169,17 @@ def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_pass
             break
         mv = model.leaf_moves(z[None, :], prices=prices[None, :], max_moves=int(width))
         k = int(mv["n_moves"][0])
+        cand = [(int(mv["kind"][0, q]), int(mv["fn"][0, q]), int(mv["node"][0, q]), float(mv["delta"][0, q]))
+                for q in range(k)]
+        if swaps > 0:
+            sw = model.leaf_swaps(z[None, :], prices=prices[None, :], per_fn=int(per_fn), max_moves=int(swaps))
+            cand += [(3, int(sw["fn"][0, q]), int(sw["to"][0, q]), float(sw["delta"][0, q]), int(sw["from"][0, q]))
+                     for q in range(int(sw["n_moves"][0]))]
+            k = len(cand)
         if k == 0:
             break
         out["passes"] += 1
-        Z = np.stack([apply_move(z, F, N, has_n, mv["kind"][0, q], mv["fn"][0, q], mv["node"][0, q])
-                      for q in range(k)])
+        Z = np.stack([apply_move(z, F, N, has_n, c[0], c[1], c[2], *c[4:]) for c in cand])
         r = model.leaf_eval(Z, rounds=rounds, cutoff=upper, prices=np.tile(prices, (k, 1)) if warm else None,
                             repair_every=repair_every)
         out["evaluated"] += k
@@ -178,8 +196,7 @@ def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_pass
         entries = model.leaf_routing(q)
         z, upper, lower = Z[q], float(ups[q]), float(r["lower"][q])
         prices = np.array(r["prices"][q], np.float64, copy=True)
-        out["accepted"].append((int(mv["kind"][0, q]), int(mv["fn"][0, q]), int(mv["node"][0, q]),
-                                float(mv["delta"][0, q]), upper))
+        out["accepted"].append(cand[q][:4] + (upper,) + cand[q][4:])
         if log is not None:
             log(f"placement search: pass {out['passes']} move {out['accepted'][-1][:3]} upper {upper:.10g}")
     out.update(z=z, upper=upper, lower=lower, row=entries[0], dst=entries[1], val=entries[2])

@@ -304,7 +304,7 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_lp_rc_fixings", "nep_debug_block_split", "nep_leaf_eval", "nep_leaf_routing_entries",
            "nep_debug_leaf_repair", "nep_bnb_set_leaf_engine", "nep_bnb_get_leaf_stats", "nep_bnb_incumbent_routing",
            "nep_leaf_eval_ex", "nep_debug_leaf_repair_from", "nep_leaf_moves", "nep_debug_leaf_move_list",
-           "nep_debug_fac_state")
+           "nep_debug_fac_state", "nep_leaf_swaps", "nep_debug_leaf_swap_list")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -406,6 +406,8 @@ def load_library(path=None):
                                                pi32, _dp, _dp]
     lib.nep_leaf_moves.argtypes = [vp, i32, _dp, _dp, i32, pi32, pi32, pi32, pi32, _dp, _dp, _dp]
     lib.nep_debug_leaf_move_list.argtypes = [ctypes.POINTER(ModelDesc), _dp, _dp, i32, pi32, pi32, pi32, pi32, _dp]
+    lib.nep_leaf_swaps.argtypes = [vp, i32, _dp, _dp, i32, i32, pi32, pi32, pi32, pi32, _dp, _dp, _dp, pi32]
+    lib.nep_debug_leaf_swap_list.argtypes = [i32, i32, _dp, pi32, i32, i32, pi32, pi32, pi32, pi32, _dp]
     lib.nep_last_error.restype = ctypes.c_char_p
     lib.nep_api_version.restype = ctypes.c_int
     # array arguments travel as plain addresses (_ptr: the array's data pointer as an int): ctypes' typed
@@ -603,6 +605,25 @@ def debug_leaf_move_list(data, variant, z, table, max_moves, alpha=0.5, step=STE
                                              _ptr(node, ctypes.c_int32), _ptr(delta)), "nep_debug_leaf_move_list")
     n = int(cnt[0])
     return {"n_moves": n, "kind": kind[:n], "fn": fn[:n], "node": node[:n], "delta": delta[:n]}
+
+
+def debug_leaf_swap_list(best, best_from, per_fn, max_moves):
+    """Host-only (no GPU needed): the swap list (nep_debug_leaf_swap_list) of one placement from its tables best [F, N]
+    and best_from [F, N] (nep_leaf_swaps' selection of the per_fn cheapest per function, and its merge).  Returns
+    dict(n_moves, fn, from, to, delta) with the arrays at their full length max_moves (-1 / inf past n_moves)."""
+    lib = load_library()
+    best = np.ascontiguousarray(np.asarray(best, np.float64))
+    F, N = best.shape
+    best_from = np.ascontiguousarray(np.asarray(best_from, np.int32).reshape(F, N))
+    mm = int(max_moves)
+    cnt = np.zeros(1, np.int32)
+    fn, src, to = (np.zeros(max(mm, 0), np.int32) for _ in range(3))
+    delta = np.zeros(max(mm, 0))
+    _check(lib, lib.nep_debug_leaf_swap_list(F, N, _ptr(best), _ptr(best_from, ctypes.c_int32), int(per_fn), mm,
+                                             _ptr(cnt, ctypes.c_int32), _ptr(fn, ctypes.c_int32),
+                                             _ptr(src, ctypes.c_int32), _ptr(to, ctypes.c_int32), _ptr(delta)),
+           "nep_debug_leaf_swap_list")
+    return {"n_moves": int(cnt[0]), "fn": fn, "from": src, "to": to, "delta": delta}
 
 
 def debug_block_split(n_nodes, n_functions, na, relaxation=RELAX_REFERENCE):
@@ -844,6 +865,32 @@ class LPModel:
         out = {"n_moves": cnt, "kind": kind, "fn": fn, "node": node, "delta": delta, "lagr": lagr}
         if table:
             out["table"] = tab
+        return out
+
+    def leaf_swaps(self, z, prices=None, per_fn=4, max_moves=64, table=False):
+        """The priced swaps (nep_leaf_swaps) of placements z [n, n_int] of a step-1 reference model at prices [n, N]
+        >= 0 (None: zeros): function fn leaves its open destination `from` for the closed one `to`, priced jointly.
+        The device keeps the per_fn (1 .. 8) cheapest destinations per function; dict of n_moves [n], fn / from / to
+        [n, max_moves] (-1 past n_moves), delta [n, max_moves] (the exact change of the Lagrangian bound at these
+        prices, ascending; inf past n_moves), lagr [n] (that bound) and, with table=True, best [n, F, N] (the
+        cheapest swap of f into j; inf: open for f, or screened) and best_from [n, F, N] (its source node, -1: none).
+        Without table no [F, N] array leaves the device."""
+        z = np.ascontiguousarray(np.asarray(z, np.float64).reshape(-1, self.n_int))
+        n, mm = len(z), int(max_moves)
+        pin = None if prices is None else np.ascontiguousarray(np.asarray(prices, np.float64).reshape(n, self.N))
+        cnt = np.zeros(n, np.int32)
+        fn, src, to = (np.zeros((n, max(mm, 0)), np.int32) for _ in range(3))
+        delta, lagr = np.zeros((n, max(mm, 0))), np.zeros(n)
+        best = np.zeros((n, self.F, self.N)) if table else None
+        bfrom = np.zeros((n, self.F, self.N), np.int32) if table else None
+        _check(self._lib, self._lib.nep_leaf_swaps(self._h, n, _ptr(z), _ptr(pin), int(per_fn), mm,
+                                                   _ptr(cnt, ctypes.c_int32), _ptr(fn, ctypes.c_int32),
+                                                   _ptr(src, ctypes.c_int32), _ptr(to, ctypes.c_int32), _ptr(delta),
+                                                   _ptr(lagr), _ptr(best), _ptr(bfrom, ctypes.c_int32)),
+               "nep_leaf_swaps")
+        out = {"n_moves": cnt, "fn": fn, "from": src, "to": to, "delta": delta, "lagr": lagr}
+        if table:
+            out["best"], out["best_from"] = best, bfrom
         return out
 
     def leaf_routing(self, k):

@@ -100,6 +100,9 @@ class NeptuneStepBase(Solver):
     # moves"): 0 off; a width > 0: from the cheapest capacity-greedy leaf, that many priced moves evaluated per pass,
     # its end point appended to the root's primal items.  Off until its product runs are weighed over more seeds
     placement_search = 0
+    # priced swaps asked for per pass of that search beside its single moves (nep_leaf_swaps; DESIGN.md §7 "Priced
+    # swaps"): 0 off
+    placement_swaps = 0
 
     # bound-model slots beyond the `batch` in flight and its root's: finished branching nodes' states stay there
     # (least recently finished reused first) so their children warm-start from them (DESIGN.md §7 "Parked parents")
@@ -235,7 +238,8 @@ class NeptuneStepBase(Solver):
                 return items
             z0 = np.zeros(model.n_int)
             z0[np.asarray(items[0][0])] = items[0][1]
-            res = placement_search(model, z0, width=int(self.placement_search), log=self.log)
+            res = placement_search(model, z0, width=int(self.placement_search), log=self.log,
+                                   swaps=int(self.placement_swaps))
             if not res["accepted"]:
                 return items
             zs = res["z"]

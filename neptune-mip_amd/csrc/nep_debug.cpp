@@ -152,6 +152,22 @@ int nep_debug_leaf_move_list(const nep_model_desc *desc, const double *z_leaf, c
   return NEP_OK;
 }
 
+int nep_debug_leaf_swap_list(int32_t F, int32_t N, const double *best, const int32_t *best_from, int32_t per_fn,
+                             int32_t max_moves, int32_t *n_moves, int32_t *fn, int32_t *from, int32_t *to,
+                             double *delta) {
+  if (!best || !best_from || !n_moves) return fail(NEP_ERR_ARG, "null argument");
+  if (F < 1 || N < 1) return fail(NEP_ERR_ARG, "bad F or N");
+  if (per_fn < 1 || per_fn > kLeafSwapPerFn)
+    return fail(NEP_ERR_ARG, "per_fn must be 1 .. " + std::to_string(kLeafSwapPerFn));
+  if (max_moves < 0) return fail(NEP_ERR_ARG, "max_moves must be >= 0");
+  if (max_moves > 0 && (!fn || !from || !to || !delta)) return fail(NEP_ERR_ARG, "null argument");
+  std::vector<LeafSwap> sw;
+  if (max_moves > 0) leaf_swap_select(F, N, best, best_from, per_fn, sw);
+  leaf_swap_merge(sw, max_moves);
+  leaf_swaps_out(sw, max_moves, n_moves, fn, from, to, delta);
+  return NEP_OK;
+}
+
 int nep_debug_presolve(const nep_model_desc *desc, int32_t n, const double *lbi, const double *ubi, int32_t *ok_full,
                        int32_t *ok_node, double *box_full, double *box_node) {
   if (!desc || n < 0 || !ok_full || !ok_node) return fail(NEP_ERR_ARG, "null argument");

@@ -60,7 +60,8 @@ hipError_t launch_power_iteration(const DeviceView &v, int iters, double *zx, do
                                   double *out, const int32_t *rp, const int32_t *ci, const double *cv,
                                   const int32_t *cp, const int32_t *ri, const double *rv, hipStream_t s);
 
-// nep_leaf.hip, nep_leaf_heur.hip, nep_leaf_moves.hip — the fixed-placement evaluator; *_lds: a kernel's dynamic LDS
+// nep_leaf.hip, nep_leaf_heur.hip, nep_leaf_moves.hip, nep_leaf_swaps.hip — the fixed-placement evaluator; *_lds: a
+// kernel's dynamic LDS
 size_t leaf_assign_lds(int N);
 hipError_t launch_leaf_rounds(const LeafView &v, int rounds, int threads, hipStream_t s, const LeafHeurView *heur);
 size_t leaf_repair_lds(int N);
@@ -68,5 +69,7 @@ hipError_t launch_leaf_heur_init(const LeafView &v, const LeafHeurView &h, hipSt
 hipError_t launch_leaf_repair(const LeafView &v, const LeafHeurView &h, int rd, hipStream_t s);
 size_t leaf_moves_lds(int N);
 hipError_t launch_leaf_moves(const LeafView &v, int threads, hipStream_t s);
+size_t leaf_swaps_lds(int N);
+hipError_t launch_leaf_swaps(const LeafView &v, const LeafSwapView &sv, int threads, hipStream_t s);
 
 }  // namespace nep

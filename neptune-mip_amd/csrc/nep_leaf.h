@@ -106,7 +106,8 @@ struct LeafMove {
   double delta;             // L(C', y) - L(C, y)
 };
 
-// leaf_moves' dynamic LDS (56 (N + 1) + 16 bytes) is held to this: N <= 1169 (nep_leaf_moves refuses a wider model)
+// leaf_moves' and leaf_swaps' dynamic LDS (56 (N + 1) + 16 bytes each) is held to this: N <= 1169 (nep_leaf_moves and
+// nep_leaf_swaps refuse a wider model)
 constexpr size_t kLeafMovesLdsCap = 64 * 1024;
 
 // what the move screens need beyond LeafInstance: the evaluator's INFEASIBLE rules on memory and budget
@@ -120,5 +121,41 @@ struct LeafLimits {
 // node, fn) order, at most max_moves of them
 void leaf_move_list(const LeafInstance &in, const LeafLimits &lim, const uint8_t *c_open, const double *table,
                     int max_moves, std::vector<LeafMove> &out);
+
+// Priced swaps of a placement (nep_leaf_swaps; nep_leaf_swaps.hip prices and selects, nep_leaf_swaps.cpp merges): a
+// swap moves function fn from its open destination `from` to a closed one `to`.  At most kLeafSwapPerFn per function
+// leave the device.
+constexpr int kLeafSwapPerFn = 8;
+
+// one selected swap of a (placement, function) on the device (+inf, -1, -1: none)
+struct LeafSwapRec {
+  double delta;
+  int32_t from, to;
+};
+
+struct LeafSwap {
+  int32_t fn, from, to;
+  double delta;   // L(C', y) - L(C, y)
+};
+
+// device arrays of the swap pricing of one chunk of placements, beside its LeafView
+struct LeafSwapView {
+  int per_fn;             // records kept per function, 1 .. kLeafSwapPerFn
+  double cn;              // cost_n (0: the variant has no n)
+  const double *fmem;     // [F] the functions' memory
+  const double *nmem1;    // [N] the nodes' memory + 1e-9 (the ADD screen's right-hand side)
+  const int32_t *ncnt;    // [B][N] placements per node; -1: an empty node whose cost is beyond the budget
+  const double *mem;      // [B][N] memory used per node, summed over its functions in ascending order
+  LeafSwapRec *rec;       // [B][F][per_fn] the cheapest swaps per function, ascending (delta, to)
+  double *best;           // [B][F][N] or nullptr: the cheapest swap of f into j' (+inf: open, or screened)
+  int32_t *best_from;     // [B][F][N] or nullptr: its source node (-1: none)
+};
+
+// the per_fn cheapest (delta, to) per function of the tables best / best_from [F][N], appended to out in the kernel's
+// order (functions ascending, then ascending (delta, to))
+void leaf_swap_select(int F, int N, const double *best, const int32_t *best_from, int per_fn,
+                      std::vector<LeafSwap> &out);
+// out in ascending (delta, fn, to, from) order, cut to max_moves
+void leaf_swap_merge(std::vector<LeafSwap> &out, int max_moves);
 
 }  // namespace nep

@@ -1,7 +1,7 @@
 // nep_leaf_host.cpp — the host side of the fixed-placement evaluator (nep_leaf_eval, nep_leaf_routing_entries,
-// nep_leaf_moves): argument checks, the device workspace, staging of a chunk of placements, the launches
-// of nep_leaf.hip / nep_leaf_heur.hip / nep_leaf_moves.hip and the read-outs through nep_leaf_repair.cpp /
-// nep_leaf_moves.cpp.
+// nep_leaf_moves, nep_leaf_swaps): argument checks, the device workspace, staging of a chunk of
+// placements, the launches of nep_leaf.hip / nep_leaf_heur.hip / nep_leaf_moves.hip / nep_leaf_swaps.hip and the
+// read-outs through nep_leaf_repair.cpp / nep_leaf_moves.cpp / nep_leaf_swaps.cpp.
 #include "nep_model.h"
 
 using namespace nep;
@@ -38,22 +38,23 @@ bool leaf_binary(const Model &m, const double *z, uint8_t *c_open, double *nsum)
 // a row without x rejects the placement: C3 memory, C6/C7 n against c, C8 budget, a function without a destination
 bool leaf_rejects(const Model &m, const double *z, const uint8_t *c_open) {
   const int N = m.N, F = m.F;
+  // (c is walked along its rows: a node's memory still sums over its functions in ascending order)
+  std::vector<double> mem(N, 0.0);
+  std::vector<uint8_t> any(N, 0);
+  for (int f = 0; f < F; ++f) {
+    const uint8_t *cf = c_open + (size_t)f * N;
+    bool dest = false;
+    for (int j = 0; j < N; ++j)
+      if (cf[j]) { mem[j] += m.mem_f[f]; any[j] = 1; dest = true; }
+    if (!dest) return true;
+  }
   for (int j = 0; j < N; ++j) {
-    double mem = 0.0;
-    bool any = false;
-    for (int f = 0; f < F; ++f)
-      if (c_open[(size_t)f * N + j]) { mem += m.mem_f[f]; any = true; }
-    if (mem > m.capn[j] + 1e-9) return true;
+    if (mem[j] > m.capn[j] + 1e-9) return true;
     if (m.has_n) {
       const double nj = z[m.il.on + j];
-      if (any != (nj != 0.0)) return true;
+      if ((any[j] != 0) != (nj != 0.0)) return true;
       if (m.node_cost[j] * nj > m.node_budget + 1e-9) return true;
     }
-  }
-  for (int f = 0; f < F; ++f) {
-    bool any = false;
-    for (int j = 0; j < N && !any; ++j) any = c_open[(size_t)f * N + j] != 0;
-    if (!any) return true;
   }
   return false;
 }
@@ -178,7 +179,7 @@ static int ensure_leaf_heur(Model &m, int rounds) {
   return NEP_OK;
 }
 
-// The argument checks nep_leaf_eval_ex and nep_leaf_moves share, in the order both make them: the model's kind, n, the
+// The argument checks nep_leaf_eval_ex, nep_leaf_moves and nep_leaf_swaps share, in the order both make them: the model's kind, n, the
 // entry's own checks (own_checks, between the two), every entry of z_leaf 0 or 1, every price finite and >= 0
 // (prices_name: the argument's name in the message).
 template <typename OwnChecks>
@@ -387,6 +388,26 @@ void leaf_moves_out(const std::vector<LeafMove> &mv, int max_moves, int32_t *n_m
   }
 }
 
+// L(C, y) = cost_n sum n + the functions' minima - y . cores, as leaf_step sums it per thread
+static double leaf_lagr(const Model &m, const double *fpart, const double *y, const double *cores, double nsum) {
+  double sf = 0.0, sy = 0.0;
+  for (int f = 0; f < m.F; ++f) sf += fpart[f];
+  for (int j = 0; j < m.N; ++j) sy += y[j] * cores[j];
+  return (m.has_n ? m.cost_n * nsum : 0.0) + sf - sy;
+}
+
+// a pricing kernel keeps five doubles and four ints per destination / row in LDS and is held to the 64 KiB a launch
+// gets without asking for more (the evaluator's own 36 bytes fit every admitted N)
+static int leaf_check_lds(const Model &m, const char *entry, size_t (*lds)(int)) {
+  if (lds(m.N) <= kLeafMovesLdsCap) return NEP_OK;
+  int nmax = m.N;
+  while (nmax > 1 && lds(nmax) > kLeafMovesLdsCap) --nmax;
+  return fail(NEP_ERR_ARG, std::string(entry) + ": n_nodes " + std::to_string(m.N) + " needs " +
+                               std::to_string(lds(m.N)) + " bytes of LDS per workgroup, above " +
+                               std::to_string(kLeafMovesLdsCap) + " (largest supported n_nodes: " +
+                               std::to_string(nmax) + ")");
+}
+
 }  // namespace nep
 
 extern "C" {
@@ -399,17 +420,7 @@ int nep_leaf_moves(void *model, int32_t n, const double *z_leaf, const double *p
   int rc = leaf_check_args(m, n, z_leaf, prices, "prices", [&]() -> int {
     if (max_moves < 0) return fail(NEP_ERR_ARG, "max_moves must be >= 0");
     if (max_moves > 0 && (!kind || !fn || !node || !delta)) return fail(NEP_ERR_ARG, "null argument");
-    // the kernel keeps five doubles and four ints per destination / row in LDS and is held to the 64 KiB a launch
-    // gets without asking for more (the evaluator's own 36 bytes fit every admitted N)
-    if (leaf_moves_lds(m.N) > kLeafMovesLdsCap) {
-      int nmax = m.N;
-      while (nmax > 1 && leaf_moves_lds(nmax) > kLeafMovesLdsCap) --nmax;
-      return fail(NEP_ERR_ARG, "nep_leaf_moves: n_nodes " + std::to_string(m.N) + " needs " +
-                                   std::to_string(leaf_moves_lds(m.N)) + " bytes of LDS per workgroup, above " +
-                                   std::to_string(kLeafMovesLdsCap) + " (largest supported n_nodes: " +
-                                   std::to_string(nmax) + ")");
-    }
-    return NEP_OK;
+    return leaf_check_lds(m, "nep_leaf_moves", leaf_moves_lds);
   });
   if (rc) return rc;
   const size_t N = m.N, F = m.F;
@@ -448,17 +459,176 @@ int nep_leaf_moves(void *model, int32_t n, const double *z_leaf, const double *p
     for (int q = 0; q < B; ++q) {
       const int b = todo[t0 + q];
       const double *tb = w.h_table + q * F * N;
-      if (lagr) {   // L(C, y) = cost_n sum n + the functions' minima - y . cores, as leaf_step sums it per thread
-        double sf = 0.0, sy = 0.0;
-        for (size_t f = 0; f < F; ++f) sf += w.h_fpart[q * F + f];
-        for (size_t j = 0; j < N; ++j) sy += w.h_y[q * N + j] * in.cores[j];
-        lagr[b] = (m.has_n ? m.cost_n * nsums[q] : 0.0) + sf - sy;
-      }
+      if (lagr) lagr[b] = leaf_lagr(m, w.h_fpart + q * F, w.h_y + q * N, in.cores, nsums[q]);
       if (table) std::memcpy(table + b * F * N, tb, F * N * sizeof(double));
       mv.clear();
       if (max_moves > 0) leaf_move_list(in, lim, w.h_open + q * F * N, tb, max_moves, mv);
       leaf_moves_out(mv, max_moves, n_moves + b, kind + (size_t)b * max_moves, fn + (size_t)b * max_moves,
                      node + (size_t)b * max_moves, delta + (size_t)b * max_moves);
+    }
+  }
+  return NEP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// priced swaps of a placement (nep_leaf_swaps.hip, nep_leaf_swaps.cpp; DESIGN.md §7 "Priced swaps")
+// ---------------------------------------------------------------------------------------------
+namespace nep {
+
+void leaf_swaps_out(const std::vector<LeafSwap> &sw, int max_moves, int32_t *n_moves, int32_t *fn, int32_t *from,
+                    int32_t *to, double *delta) {
+  *n_moves = (int32_t)sw.size();
+  for (int q = 0; q < max_moves; ++q) {
+    const bool has = q < (int)sw.size();
+    fn[q] = has ? sw[q].fn : -1;
+    from[q] = has ? sw[q].from : -1;
+    to[q] = has ? sw[q].to : -1;
+    delta[q] = has ? sw[q].delta : INF;
+  }
+}
+
+}  // namespace nep
+
+// the swaps' workspace, on the first call: the memory figures of the ADD screens, a chunk's node state and records
+static int ensure_leaf_swaps(Model &m) {
+  Model::LeafWork &w = *m.leaf;
+  if (w.swaps) return NEP_OK;
+  const size_t N = m.N, F = m.F, B = w.cap, n0 = m.allocs.size();
+  LeafSwapView sv{};
+  std::vector<double> fmem(m.mem_f.begin(), m.mem_f.begin() + F), nmem1(N);
+  for (size_t j = 0; j < N; ++j) nmem1[j] = m.capn[j] + 1e-9;
+  int32_t *ncnt = nullptr;
+  double *mem = nullptr;
+  int rc = upload(m, &sv.fmem, fmem);
+  if (!rc) rc = upload(m, &sv.nmem1, nmem1);
+  if (!rc) rc = dalloc(m, &ncnt, B * N);
+  if (!rc) rc = dalloc(m, &mem, B * N);
+  if (!rc) rc = dalloc(m, &sv.rec, B * F * kLeafSwapPerFn);
+  // pinned: [rec | fpart | mem | ncnt]
+  void *pin = nullptr;
+  if (!rc && hipHostMalloc(&pin, B * (F * kLeafSwapPerFn * sizeof(LeafSwapRec) + F * sizeof(double) +
+                                      N * (sizeof(double) + sizeof(int32_t))) + 64) != hipSuccess)
+    rc = fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, priced swaps)");
+  if (rc) return leaf_allocs_rollback(m, n0, rc);
+  sv.ncnt = ncnt;
+  sv.mem = mem;
+  sv.cn = m.has_n ? m.cost_n : 0.0;
+  w.sv = sv;
+  w.pinned_s = pin;
+  char *p = static_cast<char *>(pin);
+  w.h_rec = reinterpret_cast<LeafSwapRec *>(p); p += B * F * kLeafSwapPerFn * sizeof(LeafSwapRec);
+  w.h_sfpart = reinterpret_cast<double *>(p); p += B * F * sizeof(double);
+  w.h_mem = reinterpret_cast<double *>(p); p += B * N * sizeof(double);
+  w.h_ncnt = reinterpret_cast<int32_t *>(p);
+  w.swaps = true;
+  return NEP_OK;
+}
+
+// the tables' part of it, on the first call that asks for them
+static int ensure_leaf_swap_tables(Model &m) {
+  Model::LeafWork &w = *m.leaf;
+  if (w.pinned_st) return NEP_OK;
+  const size_t N = m.N, F = m.F, B = w.cap;
+  if (!w.d_sfrom) {
+    const int rc = dalloc(m, &w.d_sfrom, B * F * N);
+    if (rc) return rc;
+  }
+  if (hipHostMalloc(&w.pinned_st, B * F * N * (sizeof(double) + sizeof(int32_t))) != hipSuccess) {
+    w.pinned_st = nullptr;
+    return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, swap tables)");
+  }
+  w.h_sbest = static_cast<double *>(w.pinned_st);
+  w.h_sfrom = reinterpret_cast<int32_t *>(w.h_sbest + B * F * N);
+  return NEP_OK;
+}
+
+extern "C" {
+
+int nep_leaf_swaps(void *model, int32_t n, const double *z_leaf, const double *prices, int32_t per_fn,
+                   int32_t max_moves, int32_t *n_moves, int32_t *fn, int32_t *from, int32_t *to, double *delta,
+                   double *lagr, double *best, int32_t *best_from) {
+  if (!model || !z_leaf || !n_moves) return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  int rc = leaf_check_args(m, n, z_leaf, prices, "prices", [&]() -> int {
+    if (per_fn < 1 || per_fn > kLeafSwapPerFn)
+      return fail(NEP_ERR_ARG, "per_fn must be 1 .. " + std::to_string(kLeafSwapPerFn));
+    if (max_moves < 0) return fail(NEP_ERR_ARG, "max_moves must be >= 0");
+    if (max_moves > 0 && (!fn || !from || !to || !delta)) return fail(NEP_ERR_ARG, "null argument");
+    return leaf_check_lds(m, "nep_leaf_swaps", leaf_swaps_lds);
+  });
+  if (rc) return rc;
+  const size_t N = m.N, F = m.F;
+  const bool tables = best || best_from;
+  if ((rc = ensure_leaf(m))) return rc;
+  if ((rc = ensure_leaf_swaps(m))) return rc;
+  if (tables && (rc = ensure_leaf_swap_tables(m))) return rc;
+  Model::LeafWork &w = *m.leaf;
+  const LeafInstance in = leaf_instance(m);
+  const LeafLimits lim = leaf_limits(m);
+  std::vector<LeafSwap> sw;
+  const auto out = [&](int b) {
+    leaf_swaps_out(sw, max_moves, n_moves + b, fn + (size_t)b * max_moves, from + (size_t)b * max_moves,
+                   to + (size_t)b * max_moves, delta + (size_t)b * max_moves);
+  };
+  // the placements that reach the device
+  const std::vector<int> todo = leaf_first_pass(m, n, z_leaf, [&](int b) {
+    sw.clear();
+    out(b);
+    if (lagr) lagr[b] = INF;
+    if (best) std::fill(best + b * F * N, best + (b + 1) * F * N, INF);
+    if (best_from) std::fill(best_from + b * F * N, best_from + (b + 1) * F * N, -1);
+  });
+  std::vector<double> nsums;
+  for (size_t t0 = 0; t0 < todo.size(); t0 += w.cap) {
+    const int B = (int)std::min<size_t>(w.cap, todo.size() - t0);
+    LeafView v = w.v;
+    v.B = B;
+    if ((rc = leaf_stage_chunk(m, v, todo.data() + t0, B, z_leaf, prices, nsums))) return rc;
+    // the nodes' state behind the ADD screens: leaf_move_list's sums in its order (a node's memory over its functions
+    // ascending), c walked along its rows
+    for (int q = 0; q < B; ++q) {
+      double *mem = w.h_mem + q * N;
+      int32_t *cnt = w.h_ncnt + q * N;
+      std::fill(mem, mem + N, 0.0);
+      std::fill(cnt, cnt + N, 0);
+      for (size_t f = 0; f < F; ++f) {
+        const uint8_t *cf = w.h_open + (q * F + f) * N;
+        for (size_t j = 0; j < N; ++j)
+          if (cf[j]) { mem[j] += lim.fmem[f]; ++cnt[j]; }
+      }
+      for (size_t j = 0; j < N && in.has_n; ++j)
+        if (cnt[j] == 0 && !(lim.cost[j] <= lim.budget + 1e-9)) cnt[j] = -1;
+    }
+    LeafSwapView sv = w.sv;
+    sv.per_fn = per_fn;
+    sv.best = tables ? v.share : nullptr;
+    sv.best_from = tables ? w.d_sfrom : nullptr;
+    HIPCHK(hipMemcpyAsync(const_cast<double *>(sv.mem), w.h_mem, B * N * sizeof(double), hipMemcpyHostToDevice, m.aux));
+    HIPCHK(hipMemcpyAsync(const_cast<int32_t *>(sv.ncnt), w.h_ncnt, B * N * sizeof(int32_t), hipMemcpyHostToDevice,
+                          m.aux));
+    HIPCHK(launch_leaf_swaps(v, sv, w.threads, m.aux));
+    // the read-out: per_fn records per (placement, function); the [F][N] tables only for a caller that asked
+    HIPCHK(hipMemcpyAsync(w.h_rec, sv.rec, B * F * per_fn * sizeof(LeafSwapRec), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_sfpart, v.fpart, B * F * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+    if (tables) {
+      HIPCHK(hipMemcpyAsync(w.h_sbest, sv.best, B * F * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_sfrom, sv.best_from, B * F * N * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+    }
+    HIPCHK(hipStreamSynchronize(m.aux));
+    for (int q = 0; q < B; ++q) {
+      const int b = todo[t0 + q];
+      if (lagr) lagr[b] = leaf_lagr(m, w.h_sfpart + q * F, w.h_y + q * N, in.cores, nsums[q]);
+      if (best) std::memcpy(best + b * F * N, w.h_sbest + q * F * N, F * N * sizeof(double));
+      if (best_from) std::memcpy(best_from + b * F * N, w.h_sfrom + q * F * N, F * N * sizeof(int32_t));
+      sw.clear();
+      for (size_t k = 0; max_moves > 0 && k < F * per_fn; ++k) {
+        const LeafSwapRec &r = w.h_rec[q * F * per_fn + k];
+        if (r.to >= 0) sw.push_back(LeafSwap{(int32_t)(k / per_fn), r.from, r.to, r.delta});
+      }
+      leaf_swap_merge(sw, max_moves);
+      out(b);
     }
   }
   return NEP_OK;

@@ -56,72 +56,7 @@ __global__ void leaf_moves(LeafView v) {
   const int r0 = v.frow[f], r1 = v.frow[f + 1];
   const bool pooled = r1 > r0 && v.row_src[r1 - 1] < 0;
   const int nl = K > 0 ? r1 - r0 - (pooled ? 1 : 0) : 0;   // loaded rows; at most N
-  if (K <= kLeafLaneK) {
-    for (int row = tid; row < nl; row += blockDim.x) {
-      const int src = v.row_src[r0 + row];
-      const double w = v.W[(size_t)f * N + src], oc = v.kobj * w;
-      const double *Dr = v.D + (size_t)src * N;
-      double best = oc * Dr[oj[0]] + w * yc[0], second = INFINITY;
-      int kb = 0;
-      for (int k = 1; k < K; ++k) {
-        const double c = oc * Dr[oj[k]] + w * yc[k];
-        if (c < best) {
-          second = best;
-          best = c;
-          kb = k;
-        } else if (c < second) {
-          second = c;
-        }
-      }
-      m1[row] = best;
-      m2[row] = second;
-      wl[row] = w;
-      ocs[row] = oc;
-      kk[row] = kb;
-      srcs[row] = src;
-    }
-  } else {
-    const int wave = tid >> 6, nw = blockDim.x >> 6;
-    for (int row = wave; row < nl; row += nw) {
-      const int src = v.row_src[r0 + row];
-      const double w = v.W[(size_t)f * N + src], oc = v.kobj * w;
-      const double *Dr = v.D + (size_t)src * N;
-      double best = INFINITY, second = INFINITY;
-      int kb = 0x7fffffff;
-      for (int k = lane; k < K; k += 64) {
-        const double c = oc * Dr[oj[k]] + w * yc[k];
-        if (c < best) {
-          second = best;
-          best = c;
-          kb = k;
-        } else if (c < second) {
-          second = c;
-        }
-      }
-      // (value, index, second) butterfly: the loser's best is a candidate for the second minimum; minima are exact,
-      // so the result does not depend on the order of the merges
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(best, o, 64), os = __shfl_xor(second, o, 64);
-        const int ok = __shfl_xor(kb, o, 64);
-        if (ov < best || (ov == best && ok < kb)) {
-          second = fmin(best, os);
-          best = ov;
-          kb = ok;
-        } else {
-          second = fmin(second, ov);
-        }
-      }
-      if (lane == 0) {
-        m1[row] = best;
-        m2[row] = second;
-        wl[row] = w;
-        ocs[row] = oc;
-        kk[row] = kb;
-        srcs[row] = src;
-      }
-    }
-  }
+  leaf_row_minima(v, f, K, r0, nl, oj, yc, m1, m2, wl, ocs, kk, srcs);
   __syncthreads();
   double *table = v.share + ((size_t)b * v.F + f) * N;
   for (int j = tid; j < N; j += blockDim.x) {

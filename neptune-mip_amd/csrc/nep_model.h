@@ -206,7 +206,19 @@ struct Model {
     // [table | fpart] (on the device the table lives in v.share, dead outside an evaluator round)
     void *pinned_m = nullptr;
     double *h_table = nullptr, *h_fpart = nullptr;
+    // the priced swaps (nep_leaf_swaps; nep_leaf_swaps.hip), from their first use on: the instance's memory figures,
+    // a chunk's node state and records on the device and the pinned staging of [rec | fpart | mem | ncnt]; from the
+    // first call that asks for the tables on: best_from on the device (best lives in v.share) and the pinned staging
+    // of a chunk's [best | best_from]
+    bool swaps = false;
+    LeafSwapView sv{};
+    void *pinned_s = nullptr, *pinned_st = nullptr;
+    LeafSwapRec *h_rec = nullptr;
+    double *h_sfpart = nullptr, *h_mem = nullptr, *h_sbest = nullptr;
+    int32_t *h_ncnt = nullptr, *h_sfrom = nullptr, *d_sfrom = nullptr;
     ~LeafWork() {
+      if (pinned_s) (void)hipHostFree(pinned_s);
+      if (pinned_st) (void)hipHostFree(pinned_st);
       if (pinned) (void)hipHostFree(pinned);
       if (pinned_h) (void)hipHostFree(pinned_h);
       if (pinned_ru) (void)hipHostFree(pinned_ru);
@@ -296,4 +308,6 @@ bool leaf_rejects(const Model &m, const double *z, const uint8_t *c_open);
 void leaf_point_out(const LeafPoint &pt, int32_t *row, int32_t *dst, double *val);
 void leaf_moves_out(const std::vector<LeafMove> &mv, int max_moves, int32_t *n_moves, int32_t *kind, int32_t *fn,
                     int32_t *node, double *delta);
+void leaf_swaps_out(const std::vector<LeafSwap> &sw, int max_moves, int32_t *n_moves, int32_t *fn, int32_t *from,
+                    int32_t *to, double *delta);
 }  // namespace nep

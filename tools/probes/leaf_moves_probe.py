@@ -7,6 +7,8 @@ and the product's step-1 search with NeptuneStepBase.placement_search off and on
   python3 tools/probe.py leaf_moves_probe --descend 256x128 512x256 1024x512
                                 placement_search: repair_every None / 4 x width 16 / 64; start and end upper,
                                 passes, seconds
+  python3 tools/probe.py leaf_moves_probe --swaps 256x128 512x256      nep_leaf_swaps beside nep_leaf_moves for 1 and 32
+                                placements, then the --descend table with swaps 0 and 16 (DESIGN.md §7 "Priced swaps")
   python3 tools/probe.py leaf_moves_probe 256x128:20 512x256:60        the searches (default): width 0 and 16
 
 Every run is a child process under its own time limit; the first one that does not end well (a time limit, a non-zero
@@ -108,7 +110,43 @@ def price(size):
         m.close()
 
 
-def descend(size):
+def swaps_price(size):
+    """nep_leaf_swaps beside nep_leaf_moves on price()'s placements"""
+    from core.engine.heuristics import apply_move
+    from core.engine.lp import LPModel
+    d = _instance(size)
+    N, F = len(d.nodes), len(d.functions)
+    z0 = _greedy(d, size)[0]
+    m = LPModel(d, "MinDelayAndUtilization", step=1, alpha=0.5, max_batch=1)
+    try:
+        y = m.leaf_eval(z0[None, :], rounds=16)["prices"][0]
+        mv = m.leaf_moves(z0[None, :], prices=y[None, :], max_moves=31)     # (first calls: the stagings)
+        sw = m.leaf_swaps(z0[None, :], prices=y[None, :], per_fn=8, max_moves=8 * F, table=True)
+        Z = np.stack([z0] + [apply_move(z0, F, N, True, mv["kind"][0, q], mv["fn"][0, q], mv["node"][0, q])
+                             for q in range(int(mv["n_moves"][0]))])
+        print(f"   R = {m.info.n_rows}, open placements {int(z0[:F * N].sum())}, swaps of the start "
+              f"{int(np.isfinite(sw['best'][0]).sum())} (f, to), cheapest {sw['delta'][0, :4].tolist()}", flush=True)
+        for n_pl in (1, len(Z)):
+            P = np.tile(y, (n_pl, 1))
+            tm, _ = _best(lambda: m.leaf_moves(Z[:n_pl], prices=P, max_moves=64))
+            tp, _ = _best(lambda: m.leaf_moves(Z[:n_pl], prices=P, max_moves=0))
+            ts, _ = _best(lambda: m.leaf_swaps(Z[:n_pl], prices=P, per_fn=4, max_moves=64))
+            t8, _ = _best(lambda: m.leaf_swaps(Z[:n_pl], prices=P, per_fn=8, max_moves=64))
+            tt, _ = _best(lambda: m.leaf_swaps(Z[:n_pl], prices=P, per_fn=4, max_moves=64, table=True))
+            print(f"   n {n_pl:3d}: leaf_moves 64 moves {1e3 * tm:8.2f} ms (prices only {1e3 * tp:8.2f} ms) | leaf_swaps "
+                  f"64 swaps per_fn 4 {1e3 * ts:8.2f} ms, per_fn 8 {1e3 * t8:8.2f} ms, with the tables "
+                  f"{1e3 * tt:8.2f} ms", flush=True)
+    finally:
+        m.close()
+
+
+def swaps(size):
+    """the swaps' pricing times, then descend() without and with swaps"""
+    swaps_price(size)
+    descend(size, (0, 16))
+
+
+def descend(size, swaps_each=(0,)):
     from core.engine.heuristics import placement_search
     from core.engine.lp import LPModel
     d = _instance(size)
@@ -127,14 +165,15 @@ def descend(size):
               flush=True)
         m.leaf_moves(zs[0][None, :], max_moves=1)
         for every in (None, 4):
-            for width in (16, 64):
+            for width, nsw in ((w, s) for w in (16, 64) for s in swaps_each):
                 t0 = time.time()
                 res = placement_search(m, zs[0], rounds=32, repair_every=every, width=width, max_passes=1000,
-                                       time_limit=DESCEND_LIMIT_S)
-                kinds = np.bincount(np.asarray([a[0] for a in res["accepted"]], np.int64), minlength=3).tolist()
-                print(f"   repair_every {every} width {width:2d}: upper {res['start_upper']:.6f} -> {res['upper']:.6f} "
-                      f"(lower {res['lower']:.6f}) passes {res['passes']} evaluated {res['evaluated']} accepted "
-                      f"{len(res['accepted'])} (add, drop, close) {kinds} {time.time() - t0:.2f}s", flush=True)
+                                       time_limit=DESCEND_LIMIT_S, swaps=nsw)
+                kinds = np.bincount(np.asarray([a[0] for a in res["accepted"]], np.int64), minlength=4).tolist()
+                print(f"   repair_every {every} width {width:2d} swaps {nsw:2d}: upper {res['start_upper']:.6f} -> "
+                      f"{res['upper']:.6f} (lower {res['lower']:.6f}) passes {res['passes']} evaluated "
+                      f"{res['evaluated']} accepted {len(res['accepted'])} (add, drop, close, swap) {kinds} "
+                      f"{time.time() - t0:.2f}s", flush=True)
     finally:
         m.close()
 
@@ -182,7 +221,9 @@ def main():
         return price(a[1])
     if a[:1] == ["--descend-one"]:
         return descend(a[1])
-    if a[:1] in (["--price"], ["--descend"]):
+    if a[:1] == ["--swaps-one"]:
+        return swaps(a[1])
+    if a[:1] in (["--price"], ["--descend"], ["--swaps"]):
         for size in a[1:] or ["256x128", "512x256"]:
             if not child([a[0] + "-one", size], ALONE_LIMIT_S):
                 raise SystemExit(1)
