@@ -374,6 +374,53 @@ int nep_debug_leaf_swap_list(int32_t F, int32_t N, const double *best, const int
                              int32_t max_moves, int32_t *n_moves, int32_t *fn, int32_t *from, int32_t *to,
                              double *delta);
 
+/* The placement search as one call (csrc/nep_leaf_search.hip, csrc/nep_leaf_search.cpp; DESIGN.md §7 "Native search"):
+ * the descent of core/engine/heuristics.py placement_search over nep_leaf_eval_ex, nep_leaf_moves and nep_leaf_swaps.
+ * The current placement stays in one slot of the evaluator's chunk; the neighbours of a pass are written beside it on
+ * the device from move records, so after the start no placement crosses to the device as z.
+ * verify = 0: placement_search's results to the bit — z0 evaluated cold without a cutoff; per pass the `width` cheapest
+ * single moves at the current best prices, then the `swaps` cheapest swaps at the same prices; every neighbour evaluated
+ * with cutoff = the current upper (from the current prices when warm, else from zeros) and every one that is not cut
+ * off repaired and verified on the host; the lowest-index minimum of the verified uppers accepted when it is below
+ * upper - 1e-9 max(1, |upper|); a start without a point takes the first neighbour that has one; stops at the first pass
+ * without an acceptance, when no move exists, at max_passes or at time_limit.
+ * verify = 1 (lazy; needs repair_every >= 1): after a pass's rounds only each neighbour's bounds, flags and device
+ * objective d_q are read (48 bytes).  The candidates — not cut off, d_q finite and, for a finite upper, d_q < upper -
+ * 1e-9 max(1, |upper|) — are taken in ascending (d_q, q); for each the host copies that neighbour's round-0 and best
+ * round's assignments and loads, repairs both as nep_leaf_eval_ex does and takes the cheaper verified point; the first
+ * whose verified upper improves (a start without a point: is finite) is accepted; if none verifies the search ends.
+ * Another acceptance rule, not an approximation of soundness: every accepted point is host-verified in fp64.
+ * Outputs: z_out, upper, lower and prices_out of the end placement, start_upper, passes, evaluated (neighbours),
+ * verified (host verifications; verify = 0: the neighbours not cut off), n_accepted and per accepted move its kind, fn
+ * (-1: CLOSE), node, src (a swap's source, else -1), delta and the verified upper.  nep_leaf_routing_entries(model, 0,
+ * ...) then returns the end placement's host-verified routing (NEP_ERR_STATE without one).  NEP_ERR_ARG as
+ * nep_leaf_swaps and in its order (step-2 / facility models, the options, the 64 KiB LDS bound, an entry of z0 not 0 or
+ * 1), and for verify = 1 with repair_every = 0. */
+typedef struct {
+  int32_t rounds;        /* price rounds per evaluation (<= 0: 32) */
+  int32_t repair_every;  /* nep_leaf_heur_opts' (0: no per-round repair) */
+  int32_t width;         /* single moves per pass (nep_leaf_moves' max_moves) */
+  int32_t swaps;         /* swaps per pass (0: none), per_fn 1..8 as nep_leaf_swaps */
+  int32_t per_fn;
+  int32_t max_passes;
+  int32_t warm;          /* neighbours start from the current placement's best prices */
+  int32_t verify;        /* 0: every neighbour that is not cut off is verified on the host; 1: lazy */
+  double time_limit;     /* seconds, <= 0: none */
+} nep_leaf_search_opts;
+int nep_leaf_search(void *model, const double *z0 /* [n_int] */, const nep_leaf_search_opts *opts,
+                    double *z_out /* [n_int] */, double *upper, double *lower, double *prices_out /* [N] or NULL */,
+                    double *start_upper, int32_t *passes, int64_t *evaluated, int64_t *verified, int32_t *n_accepted,
+                    int32_t *kind, int32_t *fn, int32_t *node, int32_t *src, double *delta,
+                    double *acc_upper /* each [max_passes] */);
+/* host-only: the search's move application (it rebuilds z_out and the verified neighbours' bytes), so the CPU suite
+ * checks it against heuristics.apply_move without a GPU; z [F N (+ N where has_n)] */
+int nep_debug_leaf_apply_move(int32_t F, int32_t N, int32_t has_n, const double *z_in, int32_t kind, int32_t fn,
+                              int32_t node, int32_t src /* a swap's source, else ignored */, double *z_out);
+/* the device expansion alone: z_base staged, its n neighbours of the given moves expanded (leaf_search_expand) and read
+ * back — open_out [n][F][N] their c, nsum_out [n] the open-node count each record carried */
+int nep_debug_leaf_expand(void *model, const double *z_base, int32_t n, const int32_t *kind, const int32_t *fn,
+                          const int32_t *node, const int32_t *src, uint8_t *open_out, double *nsum_out);
+
 /* The reference's offline scorers and feasibility checkers on a slot's solution, on the device
  * (efttc/utils/objectives.py:23-98, efttc/utils/constraints_step1.py:5-133; booleans are the
  * reference's truthiness, value != 0).  out[NEP_SC_COUNT]: */

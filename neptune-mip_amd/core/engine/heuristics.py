@@ -142,7 +142,7 @@ def apply_move(z, F, N, has_n, kind, fn, node, src=None):
 
 
 def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_passes=32, time_limit=None, warm=True,
-                     log=None, swaps=0, per_fn=4):
+                     log=None, swaps=0, per_fn=4, native=False, verify="all"):
     """Local search over placements from z0 [n_int] with the fixed-placement evaluator and its priced moves (DESIGN.md
     §7 "Priced moves").  model: anything with F, N, n_int and leaf_eval / leaf_moves / leaf_routing (LPModel's
     contracts).  Per pass: the moves of the current placement at its evaluated prices, the first `width` applied, the
@@ -152,9 +152,22 @@ def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_pass
     max_passes or at time_limit seconds.  swaps > 0 (the model then has leaf_swaps too): each pass also asks for that
     many priced swaps (nep_leaf_swaps, the per_fn cheapest destinations per function) at the same prices; their
     neighbours follow the single moves' in the same leaf_eval call.  Deterministic.  Returns dict(z, upper, lower, row,
-    dst, val (the routing of z, None without a point), start_upper, passes, evaluated, accepted [(kind, fn, node,
-    delta, upper), and for a swap (3, fn, to, delta, upper, from)])."""
+    dst, val (the routing of z, None without a point), start_upper, passes, evaluated, verified, accepted [(kind, fn,
+    node, delta, upper), and for a swap (3, fn, to, delta, upper, from)]); verified counts the neighbours whose
+    host-verified upper the search used (verify="all": those that reached the device and were not cut off).
+    verify="lazy" (needs repair_every >= 1) is nep_leaf_search's lazy rule on leaf_eval's device_upper d_q: the
+    candidates are the neighbours that are not cut off with a finite d_q (below upper - 1e-9 max(1, |upper|) when upper
+    is finite), taken in ascending (d_q, q); the first whose host-verified upper improves (a start without a point: is
+    finite) is accepted, and the search ends when none does.  native=True: model.leaf_search(...) with the same
+    arguments (the descent as one native call; `log` is not called)."""
     import time
+    if verify not in ("all", "lazy"):
+        raise ValueError(f"verify must be 'all' or 'lazy', not {verify!r}")
+    if verify == "lazy" and not repair_every:
+        raise ValueError("verify='lazy' needs the device objectives of repair_every >= 1")
+    if native:
+        return model.leaf_search(z0, rounds=rounds, repair_every=repair_every, width=width, swaps=swaps, per_fn=per_fn,
+                                 max_passes=max_passes, warm=warm, verify=verify, time_limit=time_limit)
     F, N = int(model.F), int(model.N)
     has_n = int(model.n_int) == F * N + N
     t0 = time.monotonic() if time_limit is not None else 0.0
@@ -163,7 +176,7 @@ def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_pass
     upper, lower = float(r["upper"][0]), float(r["lower"][0])
     prices = np.array(r["prices"][0], np.float64, copy=True)
     entries = model.leaf_routing(0) if np.isfinite(upper) else (None, None, None)
-    out = {"start_upper": upper, "passes": 0, "evaluated": 0, "accepted": []}
+    out = {"start_upper": upper, "passes": 0, "evaluated": 0, "verified": 0, "accepted": []}
     while out["passes"] < max_passes and np.isfinite(lower):
         if time_limit is not None and time.monotonic() - t0 >= time_limit:
             break
@@ -184,7 +197,24 @@ def placement_search(model, z0, rounds=32, repair_every=None, width=16, max_pass
                             repair_every=repair_every)
         out["evaluated"] += k
         ups = np.asarray(r["upper"], np.float64)
-        if np.isfinite(upper):
+        live = (np.asarray(r["status"]) != 3) & (np.asarray(r["status"]) != 4)   # not INFEASIBLE, not CUTOFF
+        if verify == "all":
+            out["verified"] += int(live.sum())
+        if verify == "lazy":
+            dq = np.asarray(r["device_upper"], np.float64)
+            ok = live & np.isfinite(dq)
+            if np.isfinite(upper):
+                ok &= dq < upper - 1e-9 * max(1.0, abs(upper))
+            q = -1
+            for t in sorted(np.flatnonzero(ok).tolist(), key=lambda t: (dq[t], t)):
+                out["verified"] += 1
+                better = ups[t] < upper - 1e-9 * max(1.0, abs(upper)) if np.isfinite(upper) else np.isfinite(ups[t])
+                if better:
+                    q = t
+                    break
+            if q < 0:
+                break
+        elif np.isfinite(upper):
             q = int(np.argmin(ups))
             if not ups[q] < upper - 1e-9 * max(1.0, abs(upper)):
                 break

@@ -22,6 +22,7 @@ API_VERSION = 13
 RELAX_REFERENCE, RELAX_FACILITY = 0, 1
 LEAF_EXACT, LEAF_FEASIBLE, LEAF_NO_POINT, LEAF_INFEASIBLE, LEAF_CUTOFF = 0, 1, 2, 3, 4
 MOVE_ADD, MOVE_DROP, MOVE_CLOSE = 0, 1, 2
+MOVE_SWAP = 3
 
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -56,6 +57,12 @@ class LeafOpts(ctypes.Structure):
 class LeafHeurOpts(ctypes.Structure):
     """nep_leaf_heur_opts: the evaluator's per-round repair on the device (nep_leaf_eval_ex)"""
     _fields_ = [("repair_every", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class LeafSearchOpts(ctypes.Structure):
+    """nep_leaf_search_opts: the native placement search (nep_leaf_search)"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("rounds", "repair_every", "width", "swaps", "per_fn", "max_passes",
+                                              "warm", "verify")] + [("time_limit", ctypes.c_double)]
 
 
 class ModelInfo(ctypes.Structure):
@@ -304,7 +311,8 @@ EXPORTS = ("nep_model_create", "nep_model_destroy", "nep_model_get_info", "nep_l
            "nep_lp_rc_fixings", "nep_debug_block_split", "nep_leaf_eval", "nep_leaf_routing_entries",
            "nep_debug_leaf_repair", "nep_bnb_set_leaf_engine", "nep_bnb_get_leaf_stats", "nep_bnb_incumbent_routing",
            "nep_leaf_eval_ex", "nep_debug_leaf_repair_from", "nep_leaf_moves", "nep_debug_leaf_move_list",
-           "nep_debug_fac_state", "nep_leaf_swaps", "nep_debug_leaf_swap_list")
+           "nep_debug_fac_state", "nep_leaf_swaps", "nep_debug_leaf_swap_list", "nep_leaf_search",
+           "nep_debug_leaf_apply_move", "nep_debug_leaf_expand")
 SCORE_FIELDS = ("network_delay", "nodes_used", "node_cost", "bad_c_x", "bad_memory", "bad_handle", "bad_cpu",
                 "bad_n_c", "bad_budget", "handle_maxdev", "cpu_maxexcess")
 
@@ -408,6 +416,10 @@ def load_library(path=None):
     lib.nep_debug_leaf_move_list.argtypes = [ctypes.POINTER(ModelDesc), _dp, _dp, i32, pi32, pi32, pi32, pi32, _dp]
     lib.nep_leaf_swaps.argtypes = [vp, i32, _dp, _dp, i32, i32, pi32, pi32, pi32, pi32, _dp, _dp, _dp, pi32]
     lib.nep_debug_leaf_swap_list.argtypes = [i32, i32, _dp, pi32, i32, i32, pi32, pi32, pi32, pi32, _dp]
+    lib.nep_leaf_search.argtypes = [vp, _dp, ctypes.POINTER(LeafSearchOpts), _dp, _dp, _dp, _dp, _dp, pi32, pi64, pi64,
+                                    pi32, pi32, pi32, pi32, pi32, _dp, _dp]
+    lib.nep_debug_leaf_apply_move.argtypes = [i32, i32, i32, _dp, i32, i32, i32, i32, _dp]
+    lib.nep_debug_leaf_expand.argtypes = [vp, _dp, i32, pi32, pi32, pi32, pi32, vp, _dp]
     lib.nep_last_error.restype = ctypes.c_char_p
     lib.nep_api_version.restype = ctypes.c_int
     # array arguments travel as plain addresses (_ptr: the array's data pointer as an int): ctypes' typed
@@ -605,6 +617,18 @@ def debug_leaf_move_list(data, variant, z, table, max_moves, alpha=0.5, step=STE
                                              _ptr(node, ctypes.c_int32), _ptr(delta)), "nep_debug_leaf_move_list")
     n = int(cnt[0])
     return {"n_moves": n, "kind": kind[:n], "fn": fn[:n], "node": node[:n], "delta": delta[:n]}
+
+
+def debug_leaf_apply_move(z, F, N, has_n, kind, fn, node, src=None):
+    """Host-only (no GPU needed): the native search's move application (nep_debug_leaf_apply_move) on the placement z
+    [F N (+ N where has_n)]; core.engine.heuristics.apply_move is its mirror.  Returns z'."""
+    lib = load_library()
+    z = np.ascontiguousarray(np.asarray(z, np.float64).reshape(-1))
+    out = np.zeros_like(z)
+    _check(lib, lib.nep_debug_leaf_apply_move(int(F), int(N), 1 if has_n else 0, _ptr(z), int(kind), int(fn), int(node),
+                                              -1 if src is None else int(src), _ptr(out)),
+           "nep_debug_leaf_apply_move")
+    return out
 
 
 def debug_leaf_swap_list(best, best_from, per_fn, max_moves):
@@ -892,6 +916,57 @@ class LPModel:
         if table:
             out["best"], out["best_from"] = best, bfrom
         return out
+
+    def leaf_search(self, z0, rounds=32, repair_every=None, width=16, swaps=0, per_fn=4, max_passes=32, warm=True,
+                    verify="all", time_limit=None):
+        """The placement search as one native call (nep_leaf_search; DESIGN.md §7 "Native search"): the descent of
+        core.engine.heuristics.placement_search from z0 [n_int] with the neighbours built on the device.  verify="all":
+        placement_search's results to the bit; "lazy" (needs repair_every >= 1): only the neighbours the device's own
+        objective ranks as improving are repaired and verified on the host, cheapest first, and the first that
+        verifies is accepted.  Returns placement_search's dict (z, upper, lower, prices, row, dst, val, start_upper,
+        passes, evaluated, accepted) and verified (host verifications)."""
+        if verify not in ("all", "lazy"):
+            raise ValueError(f"verify must be 'all' or 'lazy', not {verify!r}")
+        z0 = np.ascontiguousarray(np.asarray(z0, np.float64).reshape(-1))
+        if z0.size != self.n_int:
+            raise ValueError(f"z0 has {z0.size} entries, the model {self.n_int}")
+        mp = int(max_passes)
+        opts = LeafSearchOpts(int(rounds), 0 if repair_every is None else int(repair_every), int(width), int(swaps),
+                              int(per_fn), mp, 1 if warm else 0, 1 if verify == "lazy" else 0,
+                              0.0 if time_limit is None else max(float(time_limit), 1e-300))
+        z, prices = np.zeros(self.n_int), np.zeros(self.N)
+        sc = np.zeros(3)                       # upper, lower, start_upper
+        cnt32, cnt64 = np.zeros(2, np.int32), np.zeros(2, np.int64)   # passes, n_accepted; evaluated, verified
+        k = max(mp, 0)
+        kind, fn, node, src = (np.zeros(k, np.int32) for _ in range(4))
+        delta, acc = np.zeros(k), np.zeros(k)
+        _check(self._lib, self._lib.nep_leaf_search(
+            self._h, _ptr(z0), ctypes.byref(opts), _ptr(z), sc.ctypes.data, sc.ctypes.data + 8, _ptr(prices),
+            sc.ctypes.data + 16, cnt32.ctypes.data, cnt64.ctypes.data, cnt64.ctypes.data + 8, cnt32.ctypes.data + 4,
+            _ptr(kind, ctypes.c_int32), _ptr(fn, ctypes.c_int32), _ptr(node, ctypes.c_int32),
+            _ptr(src, ctypes.c_int32), _ptr(delta), _ptr(acc)), "nep_leaf_search")
+        upper = float(sc[0])
+        accepted = []
+        for q in range(int(cnt32[1])):
+            a = (int(kind[q]), int(fn[q]), int(node[q]), float(delta[q]), float(acc[q]))
+            accepted.append(a + (int(src[q]),) if kind[q] == MOVE_SWAP else a)
+        row, dst, val = self.leaf_routing(0) if math.isfinite(upper) else (None, None, None)
+        return {"start_upper": float(sc[2]), "passes": int(cnt32[0]), "evaluated": int(cnt64[0]),
+                "verified": int(cnt64[1]), "accepted": accepted, "z": z, "upper": upper, "lower": float(sc[1]),
+                "prices": prices, "row": row, "dst": dst, "val": val}
+
+    def debug_leaf_expand(self, z_base, kind, fn, node, src):
+        """The native search's device expansion alone (nep_debug_leaf_expand): the neighbours of z_base [n_int] by the
+        moves kind / fn / node / src [n].  Returns (open [n, F, N] uint8, nsum [n])."""
+        z = np.ascontiguousarray(np.asarray(z_base, np.float64).reshape(-1))
+        kind, fn, node, src = (np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1)) for a in (kind, fn, node, src))
+        n = len(kind)
+        out, nsum = np.zeros((n, self.F, self.N), np.uint8), np.zeros(n)
+        _check(self._lib, self._lib.nep_debug_leaf_expand(self._h, _ptr(z), n, _ptr(kind, ctypes.c_int32),
+                                                          _ptr(fn, ctypes.c_int32), _ptr(node, ctypes.c_int32),
+                                                          _ptr(src, ctypes.c_int32), out.ctypes.data, _ptr(nsum)),
+               "nep_debug_leaf_expand")
+        return out, nsum
 
     def leaf_routing(self, k):
         """(row, dst, val) of the routing behind upper[k] of the last leaf_eval call (nep_leaf_routing_entries;

@@ -103,6 +103,9 @@ class NeptuneStepBase(Solver):
     # priced swaps asked for per pass of that search beside its single moves (nep_leaf_swaps; DESIGN.md §7 "Priced
     # swaps"): 0 off
     placement_swaps = 0
+    # that search as one native call (nep_leaf_search; DESIGN.md §7 "Native search"): the same results, the neighbours
+    # built on the device.  Off: the Python descent
+    placement_native = False
 
     # bound-model slots beyond the `batch` in flight and its root's: finished branching nodes' states stay there
     # (least recently finished reused first) so their children warm-start from them (DESIGN.md §7 "Parked parents")
@@ -239,7 +242,7 @@ class NeptuneStepBase(Solver):
             z0 = np.zeros(model.n_int)
             z0[np.asarray(items[0][0])] = items[0][1]
             res = placement_search(model, z0, width=int(self.placement_search), log=self.log,
-                                   swaps=int(self.placement_swaps))
+                                   swaps=int(self.placement_swaps), native=bool(self.placement_native))
             if not res["accepted"]:
                 return items
             zs = res["z"]

@@ -168,6 +168,57 @@ int nep_debug_leaf_swap_list(int32_t F, int32_t N, const double *best, const int
   return NEP_OK;
 }
 
+int nep_debug_leaf_apply_move(int32_t F, int32_t N, int32_t has_n, const double *z_in, int32_t kind, int32_t fn,
+                              int32_t node, int32_t src, double *z_out) {
+  if (!z_in || !z_out) return fail(NEP_ERR_ARG, "null argument");
+  if (F < 1 || N < 1) return fail(NEP_ERR_ARG, "bad F or N");
+  if (!leaf_apply_move(F, N, has_n ? 1 : 0, z_in, kind, fn, node, src, z_out))
+    return fail(NEP_ERR_ARG, "a move out of range (kind 0 .. 3, fn, node, a swap's src)");
+  return NEP_OK;
+}
+
+int nep_debug_leaf_expand(void *model, const double *z_base, int32_t n, const int32_t *kind, const int32_t *fn,
+                          const int32_t *node, const int32_t *src, uint8_t *open_out, double *nsum_out) {
+  if (!model || !z_base || !kind || !fn || !node || !src || !open_out || !nsum_out)
+    return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  if (n < 1) return fail(NEP_ERR_ARG, "n must be at least 1");
+  const size_t N = m.N, F = m.F;
+  std::vector<uint8_t> c_open(F * N);
+  double nsum = 0.0;
+  if (!leaf_binary(m, z_base, c_open.data(), &nsum)) return fail(NEP_ERR_ARG, "a leaf fixes every c and n at 0 or 1");
+  int rc = ensure_leaf(m);
+  if (!rc) rc = ensure_leaf_search(m);
+  if (rc) return rc;
+  Model::LeafWork &w = *m.leaf;
+  if (w.cap < 2) return fail(NEP_ERR_ARG, "nep_debug_leaf_expand: the workspace holds one placement of this model");
+  LeafSearchBase base;
+  base.set(m.F, m.N, c_open.data(), m.has_n ? z_base + m.il.on : nullptr);
+  for (int q = 0; q < n; ++q)
+    if (!base.in_range(kind[q], fn[q], node[q], src[q]))
+      return fail(NEP_ERR_ARG, "move " + std::to_string(q) + " is out of range");
+  // the base into slot 0; the neighbours beside it, a chunk of free slots at a time.  cost_n = 1: LeafCtrl::base is
+  // the open-node count the record carried
+  std::memcpy(w.h_open, c_open.data(), F * N);
+  HIPCHK(hipMemcpyAsync(const_cast<uint8_t *>(w.v.open), w.h_open, F * N, hipMemcpyHostToDevice, m.aux));
+  const size_t free_slots = (size_t)w.cap - 1;
+  for (size_t q0 = 0; q0 < (size_t)n; q0 += free_slots) {
+    const int B = (int)std::min(free_slots, (size_t)n - q0);
+    for (int q = 0; q < B; ++q) w.h_mv[q] = base.record(kind[q0 + q], fn[q0 + q], node[q0 + q], src[q0 + q]);
+    const LeafView nv = leaf_view_at(w.v, 1, B);
+    const LeafSearchView xs{0, 1.0, INF, w.d_mv, w.v.open, w.v.ybest};
+    HIPCHK(hipMemcpyAsync(w.d_mv, w.h_mv, B * sizeof(LeafSearchMove), hipMemcpyHostToDevice, m.aux));
+    HIPCHK(launch_leaf_search_expand(nv, xs, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_open + F * N, nv.open, B * F * N, hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipMemcpyAsync(w.h_ctrl + 1, nv.ctrl, B * sizeof(LeafCtrl), hipMemcpyDeviceToHost, m.aux));
+    HIPCHK(hipStreamSynchronize(m.aux));
+    std::memcpy(open_out + q0 * F * N, w.h_open + F * N, B * F * N);
+    for (int q = 0; q < B; ++q) nsum_out[q0 + q] = w.h_ctrl[1 + q].base;
+  }
+  return NEP_OK;
+}
+
 int nep_debug_presolve(const nep_model_desc *desc, int32_t n, const double *lbi, const double *ubi, int32_t *ok_full,
                        int32_t *ok_node, double *box_full, double *box_node) {
   if (!desc || n < 0 || !ok_full || !ok_node) return fail(NEP_ERR_ARG, "null argument");

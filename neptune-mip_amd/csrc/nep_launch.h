@@ -9,6 +9,7 @@
 
 #include "nep_internal.h"
 #include "nep_leaf.h"
+#include "nep_leaf_search.h"
 
 namespace nep {
 
@@ -71,5 +72,12 @@ size_t leaf_moves_lds(int N);
 hipError_t launch_leaf_moves(const LeafView &v, int threads, hipStream_t s);
 size_t leaf_swaps_lds(int N);
 hipError_t launch_leaf_swaps(const LeafView &v, const LeafSwapView &sv, int threads, hipStream_t s);
+
+// nep_leaf_search.hip — the native placement search: the neighbours of the base (slot 0) from move records, the base's
+// node state for the swap screens, the accepted neighbour into slot 0
+hipError_t launch_leaf_search_expand(const LeafView &v, const LeafSearchView &s, hipStream_t st);
+hipError_t launch_leaf_node_state(const LeafView &v, const double *fmem, const uint8_t *over, int32_t *ncnt, double *mem,
+                                  hipStream_t st);
+hipError_t launch_leaf_search_adopt(const LeafView &v, int from, hipStream_t st);
 
 }  // namespace nep

@@ -1,7 +1,8 @@
 // nep_leaf_host.cpp — the host side of the fixed-placement evaluator (nep_leaf_eval, nep_leaf_routing_entries,
-// nep_leaf_moves, nep_leaf_swaps): argument checks, the device workspace, staging of a chunk of
-// placements, the launches of nep_leaf.hip / nep_leaf_heur.hip / nep_leaf_moves.hip / nep_leaf_swaps.hip and the
-// read-outs through nep_leaf_repair.cpp / nep_leaf_moves.cpp / nep_leaf_swaps.cpp.
+// nep_leaf_moves, nep_leaf_swaps, nep_leaf_search): argument checks, the device workspace, staging of a
+// chunk of placements, the launches of nep_leaf.hip / nep_leaf_heur.hip / nep_leaf_moves.hip / nep_leaf_swaps.hip /
+// nep_leaf_search.hip and the read-outs through nep_leaf_repair.cpp / nep_leaf_moves.cpp / nep_leaf_swaps.cpp /
+// nep_leaf_search.cpp.
 #include "nep_model.h"
 
 using namespace nep;
@@ -123,7 +124,7 @@ static int ensure_leaf_alloc(Model &m) {
   m.leaf = std::move(w);
   return NEP_OK;
 }
-static int ensure_leaf(Model &m) {
+int nep::ensure_leaf(Model &m) {
   if (m.leaf) return NEP_OK;
   const size_t n0 = m.allocs.size();
   return leaf_allocs_rollback(m, n0, ensure_leaf_alloc(m));
@@ -410,6 +411,20 @@ static int leaf_check_lds(const Model &m, const char *entry, size_t (*lds)(int))
 
 }  // namespace nep
 
+// the pinned staging of a chunk's [table | fpart], on the first call that reads a priced table
+static int ensure_leaf_moves(Model &m) {
+  Model::LeafWork &w = *m.leaf;
+  if (w.pinned_m) return NEP_OK;
+  const size_t N = m.N, F = m.F, B = w.cap;
+  if (hipHostMalloc(&w.pinned_m, B * (F * N + F) * sizeof(double)) != hipSuccess) {
+    w.pinned_m = nullptr;
+    return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, priced moves)");
+  }
+  w.h_table = static_cast<double *>(w.pinned_m);
+  w.h_fpart = w.h_table + B * F * N;
+  return NEP_OK;
+}
+
 extern "C" {
 
 int nep_leaf_moves(void *model, int32_t n, const double *z_leaf, const double *prices, int32_t max_moves,
@@ -425,16 +440,8 @@ int nep_leaf_moves(void *model, int32_t n, const double *z_leaf, const double *p
   if (rc) return rc;
   const size_t N = m.N, F = m.F;
   if ((rc = ensure_leaf(m))) return rc;
+  if ((rc = ensure_leaf_moves(m))) return rc;
   Model::LeafWork &w = *m.leaf;
-  if (!w.pinned_m) {
-    const size_t B = w.cap;
-    if (hipHostMalloc(&w.pinned_m, B * (F * N + F) * sizeof(double)) != hipSuccess) {
-      w.pinned_m = nullptr;
-      return fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, priced moves)");
-    }
-    w.h_table = static_cast<double *>(w.pinned_m);
-    w.h_fpart = w.h_table + B * F * N;
-  }
   const LeafInstance in = leaf_instance(m);
   const LeafLimits lim = leaf_limits(m);
   std::vector<LeafMove> mv;
@@ -631,6 +638,377 @@ int nep_leaf_swaps(void *model, int32_t n, const double *z_leaf, const double *p
       out(b);
     }
   }
+  return NEP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the native placement search (nep_leaf_search.hip, nep_leaf_search.cpp; DESIGN.md §7 "Native search")
+// ---------------------------------------------------------------------------------------------
+
+// the search's workspace, on the first call: a chunk's move records and the nodes that may not open
+int nep::ensure_leaf_search(Model &m) {
+  Model::LeafWork &w = *m.leaf;
+  if (w.search) return NEP_OK;
+  const size_t N = m.N, B = w.cap, n0 = m.allocs.size();
+  std::vector<uint8_t> over(N, 0);
+  for (size_t j = 0; j < N && m.has_n; ++j) over[j] = !(m.node_cost[j] <= m.node_budget + 1e-9);
+  const uint8_t *d_over = nullptr;
+  int rc = upload(m, &d_over, over);
+  if (!rc) rc = dalloc(m, &w.d_mv, B);
+  void *pin = nullptr;
+  if (!rc && hipHostMalloc(&pin, B * sizeof(LeafSearchMove)) != hipSuccess)
+    rc = fail(NEP_ERR_NOMEM, "hipHostMalloc (leaf evaluator, native search)");
+  if (rc) {
+    w.d_mv = nullptr;
+    return leaf_allocs_rollback(m, n0, rc);
+  }
+  w.d_over = const_cast<uint8_t *>(d_over);
+  w.pinned_q = pin;
+  w.h_mv = static_cast<LeafSearchMove *>(pin);
+  w.search = true;
+  return NEP_OK;
+}
+
+// the view of the B slots from slot s on
+LeafView nep::leaf_view_at(const LeafView &v, size_t s, int B) {
+  const size_t N = v.N, F = v.F, R = v.R;
+  LeafView o = v;
+  o.B = B;
+  o.open += s * F * N;
+  o.y += s * N; o.ybest += s * N;
+  o.share += s * F * N; o.fpart += s * F;
+  o.load += s * N; o.g += s * N;
+  o.asg0 += s * R; o.asg += s * R;
+  o.ctrl += s;
+  return o;
+}
+static LeafHeurView leaf_heur_view_at(const LeafHeurView &h, const LeafView &v, size_t s, int rounds, int every) {
+  const size_t N = v.N, F = v.F, R = v.R;
+  LeafHeurView o = h;
+  o.rounds = rounds;
+  o.every = every;
+  o.opl += s * F * N; o.opn += s * F;
+  o.flow += s * R; o.room += s * F; o.fcost += s * F;
+  o.nrows += s * R; o.asgrep += s * R; o.loadrep += s * N;
+  o.best += s;
+  o.round_upper += s * ((size_t)rounds + 1);
+  return o;
+}
+
+namespace {
+
+// one pass's candidate moves and what the device and the host found for each
+struct SearchPass {
+  std::vector<LeafSearchMove> mv;
+  std::vector<double> delta;
+  std::vector<double> lower, dq;     // LeafCtrl::best; LeafHeurBest::obj (+inf: none)
+  std::vector<uint8_t> live;         // reached the device and was not cut off
+  std::vector<int> slot, chunk;      // where its rounds ran (-1: rejected on the host)
+  void reset(size_t k) {
+    lower.assign(k, INF); dq.assign(k, INF);
+    live.assign(k, 0); slot.assign(k, -1); chunk.assign(k, -1);
+  }
+};
+
+// the read-backs of the neighbours whose chunk a later chunk of the same pass overwrote (lazy passes with more
+// neighbours than free slots)
+struct SearchKept {
+  std::vector<int32_t> asg0, asgrep;
+  std::vector<double> loadrep, ybest;
+};
+
+}  // namespace
+
+// the neighbour's point as nep_leaf_eval_ex verifies a placement's: the round-0 repair, the device round's repair from
+// its loads, the cheaper of the two
+static void search_verify(const LeafInstance &in, const uint8_t *c_open, double nsum, const int32_t *asg0,
+                          const int32_t *asgrep, const double *loadrep, LeafPoint &pt) {
+  pt = LeafPoint();
+  leaf_repair(in, c_open, nsum, asg0, pt);
+  if (!asgrep) return;
+  LeafPoint alt;
+  leaf_repair(in, c_open, nsum, asgrep, alt, loadrep);
+  if (alt.found && (!pt.found || alt.obj < pt.obj)) pt = std::move(alt);
+}
+
+extern "C" {
+
+int nep_leaf_search(void *model, const double *z0, const nep_leaf_search_opts *opts, double *z_out, double *upper,
+                    double *lower, double *prices_out, double *start_upper, int32_t *passes, int64_t *evaluated,
+                    int64_t *verified, int32_t *n_accepted, int32_t *kind, int32_t *fn, int32_t *node, int32_t *src,
+                    double *delta, double *acc_upper) {
+  if (!model || !z0 || !opts || !z_out || !upper || !lower || !start_upper || !passes || !evaluated || !verified ||
+      !n_accepted)
+    return fail(NEP_ERR_ARG, "null argument");
+  Model &m = *static_cast<Model *>(model);
+  if (m.step2 || m.fac) return fail(NEP_ERR_ARG, kLeafRefusal);
+  const int rounds = opts->rounds <= 0 ? 32 : opts->rounds, every = opts->repair_every;
+  const int width = opts->width, nswaps = opts->swaps, per_fn = opts->per_fn, max_passes = opts->max_passes;
+  const bool lazy = opts->verify == 1, warm = opts->warm != 0;
+  if (every < 0) return fail(NEP_ERR_ARG, "repair_every must be >= 0");
+  if (width < 0) return fail(NEP_ERR_ARG, "width must be >= 0");
+  if (nswaps < 0) return fail(NEP_ERR_ARG, "swaps must be >= 0");
+  if (per_fn < 1 || per_fn > kLeafSwapPerFn)
+    return fail(NEP_ERR_ARG, "per_fn must be 1 .. " + std::to_string(kLeafSwapPerFn));
+  if (max_passes < 0) return fail(NEP_ERR_ARG, "max_passes must be >= 0");
+  if (opts->verify != 0 && opts->verify != 1) return fail(NEP_ERR_ARG, "verify must be 0 (all) or 1 (lazy)");
+  if (lazy && every < 1)
+    return fail(NEP_ERR_ARG, "verify = 1 (lazy) needs the device objectives of repair_every >= 1");
+  if (max_passes > 0 && (!kind || !fn || !node || !src || !delta || !acc_upper))
+    return fail(NEP_ERR_ARG, "null argument");
+  int rc = leaf_check_lds(m, "nep_leaf_search", leaf_moves_lds);
+  if (rc) return rc;
+  const size_t N = m.N, F = m.F, R = m.R, ni = m.il.n_int;
+  for (size_t k = 0; k < ni; ++k)
+    if (z0[k] != 0.0 && z0[k] != 1.0)
+      return fail(NEP_ERR_ARG, "placement 0: entry " + std::to_string(k) + " is not 0 or 1 (a leaf fixes every c and n)");
+
+  // the start: nep_leaf_eval_ex's cold evaluation without a cutoff; it leaves z0 in slot 0 with its best prices
+  std::vector<double> z(z0, z0 + ni), prices(N, 0.0);
+  double up = INF, lo = INF;
+  {
+    const nep_leaf_opts o{rounds, INF, 0.0};
+    const nep_leaf_heur_opts h{every, 0};
+    int32_t status = 0;
+    if ((rc = nep_leaf_eval_ex(model, 1, z0, &o, every ? &h : nullptr, nullptr, &lo, &up, &status, prices.data(),
+                               nullptr, nullptr, nullptr, nullptr)))
+      return rc;
+  }
+  if ((rc = ensure_leaf_search(m))) return rc;
+  if ((rc = ensure_leaf_moves(m))) return rc;
+  if (nswaps > 0 && (rc = ensure_leaf_swaps(m))) return rc;
+  Model::LeafWork &w = *m.leaf;
+  if (w.cap < 2)
+    return fail(NEP_ERR_ARG, "nep_leaf_search: the evaluator's workspace holds one placement of this model (it needs "
+                             "the current one and a neighbour)");
+  const size_t free_slots = (size_t)w.cap - 1;
+  const LeafInstance in = leaf_instance(m);
+  const LeafLimits lim = leaf_limits(m);
+  LeafPoint cur = w.points.empty() ? LeafPoint() : std::move(w.points[0]);
+  *start_upper = up;
+  *passes = 0;
+  *evaluated = 0;
+  *verified = 0;
+  *n_accepted = 0;
+
+  LeafSearchBase base;
+  {
+    std::vector<uint8_t> c_open(F * N);
+    double nsum = 0.0;
+    leaf_binary(m, z.data(), c_open.data(), &nsum);
+    base.set(m.F, m.N, c_open.data(), m.has_n ? z.data() + m.il.on : nullptr);
+  }
+  const LeafView bv = [&] {   // the base's slot; the pricing kernels read its best prices
+    LeafView v = leaf_view_at(w.v, 0, 1);
+    v.y = w.v.ybest;
+    return v;
+  }();
+  const double cn = m.has_n ? m.cost_n : 0.0;
+  const auto t0 = std::chrono::steady_clock::now();
+  SearchPass ps;
+  SearchKept kept;
+  std::vector<LeafMove> mvl;
+  std::vector<LeafSwap> sw;
+  std::vector<int> todo, order;
+  std::vector<uint8_t> nb(F * N);
+  std::vector<double> acc_prices(N);
+  int npass = 0, nacc = 0;
+
+  while (npass < max_passes && std::isfinite(lo)) {
+    if (opts->time_limit > 0.0 &&
+        std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= opts->time_limit)
+      break;
+    // the pass's moves at the base's best prices: nep_leaf_moves' table and host composition, nep_leaf_swaps' records
+    ps.mv.clear();
+    ps.delta.clear();
+    if (width > 0) {
+      HIPCHK(launch_leaf_moves(bv, w.threads, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_table, bv.share, F * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipStreamSynchronize(m.aux));
+      leaf_move_list(in, lim, base.open.data(), w.h_table, width, mvl);
+      for (const LeafMove &q : mvl) {
+        ps.mv.push_back(base.record(q.kind, q.fn, q.node, -1));
+        ps.delta.push_back(q.delta);
+      }
+    }
+    if (nswaps > 0) {
+      LeafSwapView sv = w.sv;
+      sv.per_fn = per_fn;
+      sv.best = nullptr;
+      sv.best_from = nullptr;
+      HIPCHK(launch_leaf_node_state(bv, sv.fmem, w.d_over, const_cast<int32_t *>(sv.ncnt),
+                                    const_cast<double *>(sv.mem), m.aux));
+      HIPCHK(launch_leaf_swaps(bv, sv, w.threads, m.aux));
+      HIPCHK(hipMemcpyAsync(w.h_rec, sv.rec, F * per_fn * sizeof(LeafSwapRec), hipMemcpyDeviceToHost, m.aux));
+      HIPCHK(hipStreamSynchronize(m.aux));
+      sw.clear();
+      for (size_t k = 0; k < F * per_fn; ++k) {
+        const LeafSwapRec &r = w.h_rec[k];
+        if (r.to >= 0) sw.push_back(LeafSwap{(int32_t)(k / per_fn), r.from, r.to, r.delta});
+      }
+      leaf_swap_merge(sw, nswaps);
+      for (const LeafSwap &q : sw) {
+        if (!base.in_range(3, q.fn, q.to, q.from)) return fail(NEP_ERR_STATE, "nep_leaf_search: a swap out of range");
+        ps.mv.push_back(base.record(3, q.fn, q.to, q.from));
+        ps.delta.push_back(q.delta);
+      }
+    }
+    const size_t K = ps.mv.size();
+    if (K == 0) break;
+    ++npass;
+    *evaluated += (int64_t)K;
+    ps.reset(K);
+    todo.clear();
+    for (size_t q = 0; q < K; ++q)
+      if (!base.rejects(lim, ps.mv[q])) todo.push_back((int)q);
+    const int nchunks = (int)((todo.size() + free_slots - 1) / free_slots);
+    if (lazy && nchunks > 1) {
+      kept.asg0.resize(K * R); kept.asgrep.resize(K * R);
+      kept.loadrep.resize(K * N); kept.ybest.resize(K * N);
+    }
+    // mode 0's running choice: the lowest-index minimum of the verified uppers (a start without a point: the first)
+    int sel = -1;
+    LeafPoint sel_pt;
+    for (int ch = 0; ch < nchunks; ++ch) {
+      const size_t c0 = (size_t)ch * free_slots;
+      const int B = (int)std::min(free_slots, todo.size() - c0);
+      const bool last = ch + 1 == nchunks;
+      for (int q = 0; q < B; ++q) {
+        const int t = todo[c0 + q];
+        w.h_mv[q] = ps.mv[t];
+        ps.slot[t] = 1 + q;
+        ps.chunk[t] = ch;
+      }
+      const LeafView nv = leaf_view_at(w.v, 1, B);
+      const LeafHeurView hv = every ? leaf_heur_view_at(w.hv, w.v, 1, rounds, every) : LeafHeurView{};
+      const LeafSearchView xs{warm ? 1 : 0, cn, up, w.d_mv, bv.open, w.v.ybest};
+      HIPCHK(hipMemcpyAsync(w.d_mv, w.h_mv, B * sizeof(LeafSearchMove), hipMemcpyHostToDevice, m.aux));
+      HIPCHK(launch_leaf_search_expand(nv, xs, m.aux));
+      HIPCHK(launch_leaf_rounds(nv, rounds, w.threads, m.aux, every ? &hv : nullptr));
+      // the read-out: 48 bytes a neighbour on a lazy pass; what nep_leaf_eval_ex reads where every neighbour is
+      // verified, or where a later chunk will overwrite these slots
+      const bool bulk = !lazy || !last;
+      HIPCHK(hipMemcpyAsync(w.h_ctrl + 1, nv.ctrl, B * sizeof(LeafCtrl), hipMemcpyDeviceToHost, m.aux));
+      if (every) HIPCHK(hipMemcpyAsync(w.h_best + 1, hv.best, B * sizeof(LeafHeurBest), hipMemcpyDeviceToHost, m.aux));
+      if (bulk) {
+        HIPCHK(hipMemcpyAsync(w.h_y + N, nv.ybest, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+        HIPCHK(hipMemcpyAsync(w.h_asg0 + R, nv.asg0, B * R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+        if (every) {
+          HIPCHK(hipMemcpyAsync(w.h_loadrep + N, hv.loadrep, B * N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+          HIPCHK(hipMemcpyAsync(w.h_asgrep + R, hv.asgrep, B * R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+        }
+      }
+      HIPCHK(hipStreamSynchronize(m.aux));
+      for (int q = 0; q < B; ++q) {
+        const int t = todo[c0 + q];
+        const size_t s = 1 + (size_t)q;
+        const LeafCtrl &c = w.h_ctrl[s];
+        ps.lower[t] = c.best;
+        ps.live[t] = c.cut ? 0 : 1;
+        if (every) ps.dq[t] = w.h_best[s].obj;
+        if (c.cut) continue;
+        if (lazy) {
+          if (!last) {
+            std::memcpy(&kept.asg0[t * R], w.h_asg0 + s * R, R * sizeof(int32_t));
+            std::memcpy(&kept.asgrep[t * R], w.h_asgrep + s * R, R * sizeof(int32_t));
+            std::memcpy(&kept.loadrep[t * N], w.h_loadrep + s * N, N * sizeof(double));
+            std::memcpy(&kept.ybest[t * N], w.h_y + s * N, N * sizeof(double));
+          }
+          continue;
+        }
+        ++*verified;
+        LeafPoint pt;
+        base.neighbour(ps.mv[t], nb.data());
+        const bool rep = every && w.h_best[s].round >= 0;
+        search_verify(in, nb.data(), m.has_n ? (double)ps.mv[t].nopen : 0.0, w.h_asg0 + s * R,
+                      rep ? w.h_asgrep + s * R : nullptr, rep ? w.h_loadrep + s * N : nullptr, pt);
+        if (!pt.found) continue;
+        if (sel < 0 ? true : std::isfinite(up) && pt.obj < sel_pt.obj) {
+          sel = t;
+          sel_pt = std::move(pt);
+          std::memcpy(acc_prices.data(), w.h_y + s * N, N * sizeof(double));
+        }
+      }
+    }
+    if (lazy) {
+      // the candidates in ascending (device objective, index); the first whose verified point improves is taken
+      leaf_search_order(ps.dq, ps.live, up, order);
+      for (const int t : order) {
+        const size_t s = (size_t)ps.slot[t];
+        const int32_t *asg0, *asgrep;
+        const double *loadrep;
+        const bool here = ps.chunk[t] + 1 == nchunks;
+        if (here) {   // still in its slot: this neighbour's assignments and loads cross now
+          HIPCHK(hipMemcpyAsync(w.h_asg0 + s * R, w.v.asg0 + s * R, R * sizeof(int32_t), hipMemcpyDeviceToHost, m.aux));
+          HIPCHK(hipMemcpyAsync(w.h_asgrep + s * R, w.hv.asgrep + s * R, R * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                m.aux));
+          HIPCHK(hipMemcpyAsync(w.h_loadrep + s * N, w.hv.loadrep + s * N, N * sizeof(double), hipMemcpyDeviceToHost,
+                                m.aux));
+          HIPCHK(hipStreamSynchronize(m.aux));
+          asg0 = w.h_asg0 + s * R; asgrep = w.h_asgrep + s * R; loadrep = w.h_loadrep + s * N;
+        } else {
+          asg0 = &kept.asg0[t * R]; asgrep = &kept.asgrep[t * R]; loadrep = &kept.loadrep[t * N];
+        }
+        ++*verified;
+        LeafPoint pt;
+        base.neighbour(ps.mv[t], nb.data());
+        search_verify(in, nb.data(), m.has_n ? (double)ps.mv[t].nopen : 0.0, asg0, asgrep, loadrep, pt);
+        if (!pt.found || (std::isfinite(up) && !leaf_search_improves(pt.obj, up))) continue;
+        sel = t;
+        sel_pt = std::move(pt);
+        if (here) {
+          HIPCHK(hipMemcpyAsync(w.h_y + s * N, w.v.ybest + s * N, N * sizeof(double), hipMemcpyDeviceToHost, m.aux));
+          HIPCHK(hipStreamSynchronize(m.aux));
+          std::memcpy(acc_prices.data(), w.h_y + s * N, N * sizeof(double));
+        } else {
+          std::memcpy(acc_prices.data(), &kept.ybest[t * N], N * sizeof(double));
+        }
+        break;
+      }
+    } else if (sel >= 0 && std::isfinite(up) && !leaf_search_improves(sel_pt.obj, up)) {
+      sel = -1;
+    }
+    if (sel < 0) break;
+    // the accepted neighbour becomes the base, on the device and in the host's copy
+    const LeafSearchMove &a = ps.mv[sel];
+    int from = ps.slot[sel];
+    if (ps.chunk[sel] + 1 != nchunks) {   // a later chunk took its slot: expanded once more, its prices from the host
+      const LeafView nv = leaf_view_at(w.v, 1, 1);
+      const LeafSearchView xs{0, cn, up, w.d_mv, bv.open, w.v.ybest};
+      w.h_mv[0] = a;
+      std::memcpy(w.h_y + N, acc_prices.data(), N * sizeof(double));
+      HIPCHK(hipMemcpyAsync(w.d_mv, w.h_mv, sizeof(LeafSearchMove), hipMemcpyHostToDevice, m.aux));
+      HIPCHK(launch_leaf_search_expand(nv, xs, m.aux));
+      HIPCHK(hipMemcpyAsync(nv.ybest, w.h_y + N, N * sizeof(double), hipMemcpyHostToDevice, m.aux));
+      from = 1;
+    }
+    HIPCHK(launch_leaf_search_adopt(w.v, from, m.aux));
+    HIPCHK(hipStreamSynchronize(m.aux));
+    kind[nacc] = a.kind;
+    fn[nacc] = a.fn;
+    node[nacc] = a.node;
+    src[nacc] = a.src;
+    delta[nacc] = ps.delta[sel];
+    up = sel_pt.obj;
+    lo = ps.lower[sel];
+    acc_upper[nacc] = up;
+    ++nacc;
+    leaf_apply_move(m.F, m.N, m.has_n, z.data(), a.kind, a.fn, a.node, a.src, z.data());
+    base.accept(a);
+    cur = std::move(sel_pt);
+    prices = acc_prices;
+  }
+  // the end placement's host-verified routing is nep_leaf_routing_entries' placement 0
+  w.points.assign(1, LeafPoint());
+  w.points[0] = std::move(cur);
+  std::memcpy(z_out, z.data(), ni * sizeof(double));
+  *upper = up;
+  *lower = lo;
+  if (prices_out) std::memcpy(prices_out, prices.data(), N * sizeof(double));
+  *passes = npass;
+  *n_accepted = nacc;
   return NEP_OK;
 }
 

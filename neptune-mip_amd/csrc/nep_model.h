@@ -216,7 +216,14 @@ struct Model {
     LeafSwapRec *h_rec = nullptr;
     double *h_sfpart = nullptr, *h_mem = nullptr, *h_sbest = nullptr;
     int32_t *h_ncnt = nullptr, *h_sfrom = nullptr, *d_sfrom = nullptr;
+    // the native search (nep_leaf_search; nep_leaf_search.hip), from its first use on: a chunk's move records on the
+    // device and their pinned staging, and the nodes that may not open (leaf_node_state's -1 mark)
+    bool search = false;
+    LeafSearchMove *d_mv = nullptr, *h_mv = nullptr;
+    uint8_t *d_over = nullptr;
+    void *pinned_q = nullptr;
     ~LeafWork() {
+      if (pinned_q) (void)hipHostFree(pinned_q);
       if (pinned_s) (void)hipHostFree(pinned_s);
       if (pinned_st) (void)hipHostFree(pinned_st);
       if (pinned) (void)hipHostFree(pinned);
@@ -310,4 +317,7 @@ void leaf_moves_out(const std::vector<LeafMove> &mv, int max_moves, int32_t *n_m
                     int32_t *node, double *delta);
 void leaf_swaps_out(const std::vector<LeafSwap> &sw, int max_moves, int32_t *n_moves, int32_t *fn, int32_t *from,
                     int32_t *to, double *delta);
+int ensure_leaf(Model &m);          // the evaluator's workspace, on first use
+int ensure_leaf_search(Model &m);   // the native search's part of it (after ensure_leaf)
+LeafView leaf_view_at(const LeafView &v, size_t s, int B);   // the view of the B slots from slot s on
 }  // namespace nep

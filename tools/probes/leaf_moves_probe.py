@@ -9,6 +9,8 @@ and the product's step-1 search with NeptuneStepBase.placement_search off and on
                                 passes, seconds
   python3 tools/probe.py leaf_moves_probe --swaps 256x128 512x256      nep_leaf_swaps beside nep_leaf_moves for 1 and 32
                                 placements, then the --descend table with swaps 0 and 16 (DESIGN.md §7 "Priced swaps")
+  python3 tools/probe.py leaf_moves_probe --native 256x128 512x256     the --descend rows of width 16 three ways: the
+                                Python search, nep_leaf_search verify 0 and verify 1 (DESIGN.md §7 "Native search")
   python3 tools/probe.py leaf_moves_probe 256x128:20 512x256:60        the searches (default): width 0 and 16
 
 Every run is a child process under its own time limit; the first one that does not end well (a time limit, a non-zero
@@ -178,6 +180,42 @@ def descend(size, swaps_each=(0,)):
         m.close()
 
 
+def native(size):
+    """the --descend table's width-16 rows three ways in one process: the Python search, nep_leaf_search verify 0 and
+    verify 1 (lazy; the rows with a per-round repair only) — DESIGN.md §7 "Native search" """
+    from core.engine.heuristics import placement_search
+    from core.engine.lp import LPModel
+    d = _instance(size)
+    zs = _greedy(d, size)
+    if not zs:
+        zs = [_spread(d)]
+        if zs[0] is None:
+            print("   no capacity-greedy leaf and no spread start: nothing to search from", flush=True)
+            return
+    m = LPModel(d, "MinDelayAndUtilization", step=1, alpha=0.5, max_batch=1)
+    try:
+        # (first calls: every staging the three ways use)
+        m.leaf_search(zs[0], rounds=32, repair_every=4, width=16, swaps=16, max_passes=1, verify="lazy")
+        placement_search(m, zs[0], rounds=32, repair_every=4, width=16, swaps=16, max_passes=1)
+        for every in (None, 4):
+            for nsw in (0, 16):
+                kw = dict(rounds=32, repair_every=every, width=16, max_passes=1000, time_limit=DESCEND_LIMIT_S,
+                          swaps=nsw)
+                ways = [("python", dict(kw)), ("native verify 0", dict(kw, native=True))]
+                if every:
+                    ways.append(("native verify 1", dict(kw, native=True, verify="lazy")))
+                for way, k in ways:
+                    t0 = time.time()
+                    res = placement_search(m, zs[0], **k)
+                    secs = time.time() - t0
+                    per = 1e3 * secs / max(1, res["passes"])
+                    print(f"   repair_every {every} width 16 swaps {nsw:2d} {way:16s}: {secs:6.2f}s passes "
+                          f"{res['passes']:4d} {per:7.2f} ms/pass evaluated {res['evaluated']:6d} verified "
+                          f"{res['verified']:6d} upper {res['start_upper']:.6f} -> {res['upper']:.6f}", flush=True)
+    finally:
+        m.close()
+
+
 def search(size, secs, width):
     from core.engine.lp import LPModel
     from core.solvers.neptune.neptune_step import NeptuneStep1CPUMinDelayAndUtilization
@@ -223,7 +261,9 @@ def main():
         return descend(a[1])
     if a[:1] == ["--swaps-one"]:
         return swaps(a[1])
-    if a[:1] in (["--price"], ["--descend"], ["--swaps"]):
+    if a[:1] == ["--native-one"]:
+        return native(a[1])
+    if a[:1] in (["--price"], ["--descend"], ["--swaps"], ["--native"]):
         for size in a[1:] or ["256x128", "512x256"]:
             if not child([a[0] + "-one", size], ALONE_LIMIT_S):
                 raise SystemExit(1)
