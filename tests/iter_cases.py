@@ -27,6 +27,13 @@ VARIANT, ALPHA = "MinDelayAndUtilization", 0.5
 STEP2_KW = dict(max_score=20.0)          # (rhs 26 against a score of 48.7 at the uniform start)
 
 
+# the tight variant (memory rows C3 and the C7 rows active): see instance() and boxes()
+TIGHT_FN_MEM = (16.0, 15.0, 14.0, 13.0)
+TIGHT_NODE_MEM = 14.5
+TIGHT_LAST_FN = 3                        # the smallest function: the only one the tight leaf box forces on the last node
+WIDE_F = 67                              # node_pass sums per = ceil(F / 64) = 2 functions per group, last group short
+
+
 def model_kw(step):
     return dict(alpha=ALPHA, **(STEP2_KW if step != 1 else {}))
 
@@ -46,6 +53,88 @@ def matrix():
     runs += [(258, 2, 2, None)]
     runs += [(N, 1, 256, None) for N in full_width()]
     return runs
+
+
+def matrix_tight():
+    """Runs on the tight instance, as (N, step, slots, box, tight, functions): the n-up box alone at every width, and
+    256 slots cycling root / leaf / n-up at the widths of CPL 2 and 8."""
+    return [(N, 1, 1, 2, True, F) for N in EXTRA_CHUNK] + [(N, 1, 256, None, True, F) for N in (258, 1026)]
+
+
+def matrix_wide():
+    """The F = WIDE_F run: root and leaf on the ordinary instance.  (Not the n-up box: at this F the mirror's records
+    of it have a column deficit within the pooled / loaded shift's range at k = 49, which the mirror does not model,
+    and the tight leaf box is infeasible, 17 functions sharing each forced node of TIGHT_NODE_MEM.)"""
+    return [(26, 1, 2, None, False, WIDE_F)]
+
+
+def normalise(run):
+    """A run as (N, step, slots, box, tight, functions); box: None (slots cycle over every box of the instance) or the
+    one box of every slot."""
+    return tuple(run) + (False, F)[len(run) - 4:]
+
+
+def slot_boxes(run):
+    """Box index of every slot of a run."""
+    N, step, ns, box, tight, nf = normalise(run)
+    cyc = tuple(range(3 if tight else 2)) if box is None else (box,)
+    return np.array([cyc[s % len(cyc)] for s in range(ns)])
+
+
+def node_pass_groups(n_functions):
+    """nep_kernels.hip node_pass: a node's 64 lanes each sum per = ceil(F / 64) consecutive functions; returns (per,
+    lanes with a full share, functions of the one short lane or 0)."""
+    per = (n_functions + 63) // 64
+    return per, n_functions // per, n_functions % per
+
+
+FLOOR = 64 * 2.0 ** -24
+# Blocks of z / y that keep the bound of the whole array, max(8 d, FLOOR max(1, |mirror|)), instead of their own:
+# name -> the measured numbers and the reason.
+ABS_FLOOR_BLOCKS = {
+    "y1": "at N >= 1022 the kernel is 18 .. 128 d_B and 1.5 .. 12 x the block's bound off at single snapshots where the "
+          "block is nearly dead (N = 1022 root, k = 33: s_B 1.1e-14, d_B 3.4e-21, kernel 6.2e-20; N = 1026 tight root, "
+          "k = 33: s_B 1.9e-15, d_B 6.9e-22, kernel 8.8e-20; N = 1026 warm n-up child, k = 1: s_B 2.3e-15, d_B 1.5e-21, "
+          "kernel 3.5e-20): relative errors of 6e-6 .. 5e-5 in entries S - M c that cancel to 1e-9 of their terms, i.e. "
+          "float32 noise of the column sums, of which the emulation's d_B at one snapshot is a single sample; emulating "
+          "the float32 threshold sum and the row-by-row column sums did not raise that sample.  Every other snapshot "
+          "and width held y1 within its own bound.",
+}
+
+
+def blocks_of(m):
+    """{"z": [(name, offset, length)], "y": [...]} of a mirror model (ref_pdhg.RefModel): the blocks of the small
+    primal and of the duals that test_gpu_iterates.py compares one by one (reduced step 2 does not iterate z beyond c
+    and n; its idle disruption rows D1 / D2 / D3 are one block, which the mirror holds at 0)."""
+    FN = m.F * m.N
+    z = [("c", m.oc, FN), ("n", m.on, m.N)]
+    y = [("y1", m.o1, FN), ("y2", m.o2, FN), ("y3", m.o3, m.N), ("y5", m.o5, m.N), ("y6", m.o6, m.N),
+         ("y7", m.o7, m.N)]
+    if m.step2:
+        y += [("yD123", m.oD1, m.oD4 - m.oD1), ("yD4", m.oD4, 1), ("yS", m.oS, 1)]
+    return {"z": z, "y": y}
+
+
+def block_rows(blocks, got, ref, emu):
+    """Per block B of one array: (name, d_B = max |fp32 emulation - fp64 mirror|, s_B = max |fp64 mirror|, err = max
+    |got - fp64 mirror|, passes).  got is within max(8 d_B, FLOOR s_B) of the mirror — both terms relative to the
+    block, and never beyond the bound this comparison had before it went block by block, max(8 d, FLOOR max(1,
+    |mirror|)) with d over the whole array; a block the mirror holds at exactly 0 (s_B = 0) must be exactly 0 in got
+    (either sign of zero: -0 is the same number)."""
+    sel = np.concatenate([np.arange(o, o + n) for _, o, n in blocks])
+    d_all = float(np.abs(emu[sel] - ref[sel]).max())
+    rows = []
+    for name, o, n in blocks:
+        g, r, e = got[o:o + n], ref[o:o + n], emu[o:o + n]
+        d, s = float(np.abs(e - r).max()), float(np.abs(r).max())
+        err = np.abs(g - r)
+        if s == 0.0:
+            ok = not g.any()
+        else:
+            bound = np.minimum(max(8.0 * d, FLOOR * s), np.maximum(8.0 * d_all, FLOOR * np.maximum(1.0, np.abs(r))))
+            ok = bool((err <= bound).all())
+        rows.append((name, d, s, float(err.max()), ok))
+    return rows
 
 
 def padded(N):
@@ -82,9 +171,9 @@ def tile_waves(N, nslots, check, n_functions=F):
     return tw
 
 
-def variants(N, nslots):
+def variants(N, nslots, n_functions=F):
     """(CPL, TW, pass kind) of the x_pass launches of a cold LP batch of `nslots` slots."""
-    return {(cpl_of(N), tile_waves(N, nslots, kind == "CHECK"), kind) for kind in KINDS}
+    return {(cpl_of(N), tile_waves(N, nslots, kind == "CHECK", n_functions), kind) for kind in KINDS}
 
 
 def dispatchable():
@@ -123,8 +212,19 @@ def leaf_nodes(N):
     return sorted({j for f in range(F) for j in leaf_open(N, f)})
 
 
-def instance(N, step=1, seed=0):
+def nup_nodes(N):
+    """Nodes the n-up box opens (lb n = 1): function 2's own node of every 256-destination chunk index, and the
+    last node."""
+    return sorted(set(chunk_nodes(N, 2)) | {N - 1})
+
+
+def instance(N, step=1, seed=0, tight=False, n_functions=F):
     """Data of the N-node instance (see the module docstring); step 2: two old placements per function.
+    n_functions > 4: the further functions follow the recipe of functions 1-3 (8 loaded sources and a pooled row).
+    tight: function f needs TIGHT_FN_MEM[f % 4] memory and the nodes of nup_nodes(N) have TIGHT_NODE_MEM: at least the
+    smallest function's (the n-up box, n = 1 there, is feasible with that function alone) and below 0.3 x the
+    functions' total, so the memory rows C3 there are violated while the c, pulled up by C7 under n = 1, overshoot.
+    Neither option changes what the random generator draws: the default call returns the same data as before.
     What keeps the duals busy (the mirror's records show it; test_gpu_iterates.py asserts it):
       * y1 (C1): every entry is nonzero after the first iteration of a root LP (c = 0 under positive flow);
       * y2 (C2): function 0's own open nodes of the leaf box are 100 away from every source, itself included, so no
@@ -137,18 +237,19 @@ def instance(N, step=1, seed=0):
     D = rng.integers(1, 100, size=(N, N))
     np.fill_diagonal(D, 0)
     free = np.setdiff1d(np.arange(N), leaf_nodes(N))
-    W = np.zeros((F, N), np.int64)
+    nf = n_functions
+    W = np.zeros((nf, N), np.int64)
     W[0] = rng.integers(1, 9, size=N)
     W[0, N - 1] = 8
     loaded = {}
-    for f in range(1, F):
+    for f in range(1, nf):
         loaded[f] = np.sort(rng.choice(free, size=min(8, free.size), replace=False))
         W[f, loaded[f]] = rng.integers(1, 51, size=loaded[f].size)
-    cpr = rng.integers(10, 103, size=(F, N)) / 1024.0
+    cpr = rng.integers(10, 103, size=(nf, N)) / 1024.0
     cpr[0, N - 1] = 64 / 1024.0
     cores = rng.integers(8, 65, size=N) / 64.0
     node_mem = rng.integers(64, 257, size=N).astype(float)
-    fn_mem = rng.integers(4, 33, size=F).astype(float)
+    fn_mem = rng.integers(4, 33, size=nf).astype(float)
     for j in chunk_nodes(N, 0):
         D[:, j] = 100
     for q, j in enumerate(chunk_nodes(N, 1)):
@@ -159,19 +260,22 @@ def instance(N, step=1, seed=0):
     load = float((W * cpr.max(axis=1, keepdims=True)).sum())        # an upper bound on any routing's CPU load
     for j in (0, 8, 9):
         cores[j] = float(2 ** np.ceil(np.log2(load)))
-    node_mem[leaf_nodes(N)] = 256.0
-    d = Data([f"node_{i}" for i in range(N)], [f"ns/fn_{f}" for f in range(F)])
+    node_mem[leaf_nodes(N)] = max(256.0, float(2 ** np.ceil(np.log2(fn_mem.sum()))))     # (256 at F = 4)
+    if tight:
+        fn_mem = np.array([TIGHT_FN_MEM[f % F] for f in range(nf)])
+        node_mem[nup_nodes(N)] = TIGHT_NODE_MEM
+    d = Data([f"node_{i}" for i in range(N)], [f"ns/fn_{f}" for f in range(nf)])
     d.node_memory_matrix = node_mem
     d.function_memory_matrix = fn_mem
     d.node_delay_matrix = D
     d.workload_matrix = W
     d.cores_matrix = cpr
     d.core_per_req_matrix = cpr
-    d.max_delay_matrix = np.full(F, 1000)
-    d.response_time_matrix = np.zeros((F, N), np.int64)
+    d.max_delay_matrix = np.full(nf, 1000)
+    d.response_time_matrix = np.zeros((nf, N), np.int64)
     d.node_cores_matrix = cores
-    old = np.zeros((F, N), np.int64)
-    for f in range(F):
+    old = np.zeros((nf, N), np.int64)
+    for f in range(nf):
         old[f, rng.choice(N, size=2, replace=False)] = 1
     d.old_allocations_matrix = old if step != 1 else np.ones_like(old)
     d.node_costs = np.full(N, 5)
@@ -179,18 +283,30 @@ def instance(N, step=1, seed=0):
     return d
 
 
-def boxes(N, n_int, step=1, n_functions=F):
+def boxes(N, n_int, step=1, n_functions=F, tight=False):
     """[2, n_int] lower / upper bounds: the root box (no fixing) and the leaf-type box (c = 1 on leaf_open, 0
     elsewhere; everything else free).  Step 2 (delete: sum c may not grow past the two old placements per function)
-    leaves c free on leaf_open instead of forcing it to 1.  (n_functions > F: function f opens leaf_open(N, f % F).)"""
-    lb = np.full((2, n_int), -np.inf)
-    ub = np.full((2, n_int), np.inf)
+    leaves c free on leaf_open instead of forcing it to 1.  (n_functions > F: function f opens leaf_open(N, f % F).)
+    tight (step 1, the instance(tight=True) data): [3, n_int], the third row the n-up box — the root box with n = 1
+    forced on nup_nodes(N), so C7 (sum_f c >= n) is violated at c = 0 and y7 moves from the first iteration, the c
+    there rise until C3 (memory TIGHT_NODE_MEM) stops them, and y3 moves.  The tight leaf box forces only function
+    TIGHT_LAST_FN (the smallest) at the last node and leaves the others open there: all of them at once do not fit
+    its memory, and the engine's presolve proves such a box infeasible."""
+    nb = 3 if tight else 2
+    lb = np.full((nb, n_int), -np.inf)
+    ub = np.full((nb, n_int), np.inf)
     ub[1, :n_functions * N] = 0.0
     for f in range(n_functions):
         for j in leaf_open(N, f % F):
             ub[1, f * N + j] = 1.0
             if step == 1:
                 lb[1, f * N + j] = 1.0
+    if tight:
+        assert step == 1
+        for f in range(n_functions):
+            if f != TIGHT_LAST_FN:
+                lb[1, f * N + N - 1] = -np.inf
+        lb[2, n_functions * N + np.array(nup_nodes(N))] = 1.0
     return lb, ub
 
 

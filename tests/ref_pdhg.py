@@ -275,6 +275,21 @@ class RefModel:
                 S[self.row_f[a]] = np.add.reduce(A[a:b], axis=0)
         return S
 
+    def colsum32(self, A, tw=4):
+        """colsum as x_pass accumulates it on plain iterations: wave w of `tw` adds rows w, w + tw, ... of the function
+        in float32, one after the other, and the waves' sums are added in float32 in wave order (tw = 4: the tile of a
+        full batch, the longest chains)."""
+        f4 = np.float32
+        S = np.zeros((self.F, self.N), f4)
+        if self.R:
+            A4 = A.astype(f4)
+            starts = np.flatnonzero(np.r_[True, self.row_f[1:] != self.row_f[:-1]])
+            for a, b in zip(starts, np.r_[starts[1:], self.R]):
+                for w in range(tw):
+                    if a + w < b:
+                        S[self.row_f[a]] += np.add.reduce(A4[a + w:b:tw], axis=0, dtype=f4)
+        return S.astype(np.float64)
+
     # K·[x, z] (unscaled) and Kᵀy (unscaled)
     def K(self, x, z):
         N, F = self.N, self.F
@@ -363,6 +378,19 @@ def proj_simplex_rows_sorted(V, mask, return_theta=False):
 
 def _f32(a):
     return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _theta32(V, mask, theta):
+    """The simplex threshold (S - 1) / |S| of every row as x_pass forms it on plain iterations: the sum S over the
+    support {v > theta} and the quotient in float32 arithmetic (numpy's order of additions, not the wave's: the same
+    size of error).  The shifted point's entries reach ~10^2 (tau |g|), so S carries an absolute error of ~10^-5 that
+    rounding the fp64 threshold to float32 once does not show."""
+    f4 = np.float32
+    sup = mask & (V > theta[:, None])
+    cnt = sup.sum(axis=1)
+    S = np.where(sup, V, 0.0).astype(f4).sum(axis=1, dtype=f4)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(cnt > 0, ((S - f4(1.0)) / cnt.astype(f4)).astype(np.float64), theta)
 
 
 def _row_lagr(y, lo, hi):
@@ -491,8 +519,12 @@ def engine_certificate(m, lb, ub, fmask, y, z, xn, zn, cost_x, cost_int, const, 
     return dict(pobj=float(pobj), lagr=float(lagr), lagr_repaired=float(lr), res=float(res), deficit=deficit)
 
 
+OMEGA_TRAINED = 1024      # nep_internal.h kOmegaTrained
+
+
 def blocks(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, verbose=False, inline_reflect=False,
-           box=None, eta=None, omega0=None, rs_nec=0.8, fp32=False, engine=False):
+           box=None, eta=None, omega0=None, rs_nec=0.8, fp32=False, engine=False, start=None, warm_band=(2.0, 4.0),
+           lineage=0):
     """Same algorithm as the kernels, fp64: blocks of `check_every` iterations; iteration 0 of a block
     is the certificate iteration (a plain PDHG step whose input dual is the previous block's plain
     output), restarts take effect at iteration 1, the last iteration is plain, the others are
@@ -511,9 +543,19 @@ def blocks(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ve
     projected x̂, the packed duals y1 + y2, cpr y5 and yS the x update reads (kty), tau and lambda in the x
     update, the shifted point x - tau (wobj D - (m kx + w cy5 + wsc yS D)) evaluated term by term in float32
     arithmetic as x_pass writes it (its terms reach tau |g| ~ 10^2 and cancel, so rounding only the result would
-    miss most of the noise), the simplex threshold of the plain iterations, and, outside certificate iterations,
-    the column sums and CPU sums the duals of C1/C2/C5 take — everything else stays fp64 as on the device: the
-    difference to the fp64 run measures the fp32 noise of the iteration itself (not the kernels' summation orders)."""
+    miss most of the noise), the simplex threshold of the plain iterations (its sum over the support added and divided in float32: _theta32),
+    and, outside certificate iterations,
+    the column sums and CPU sums the duals of C1/C2/C5 take (accumulated in float32 row by row: colsum32) — everything else stays fp64 as on the device: the
+    difference to the fp64 run measures the fp32 noise of the iteration itself (not the kernels' summation orders).
+    start = (x, z, y, omega): a warm start from a parent's state, as nep_lp_submit with warm_start does it (init_slot
+    and the INIT variants of x_pass / node_pass / scalar_pass): x is projected onto the simplexes of this box's open
+    destinations (a step of length 0: closed destinations lose their mass, the rest is re-projected), z is clipped
+    into the box, y is kept, the activity and the anchors are taken from that point, the iteration count, the
+    restart bookkeeping and the best bound start afresh, and the primal weight goes on from the parent's omega within
+    the band [max(omega0 1e-5, floor omega), omega0 1e5] — warm_band = (floor, cap) of nep_lp_opts (defaults 2, 4); the
+    cap, at most cap x the parent's weight, holds only once the lineage (`lineage`: the parent's iterations and its
+    ancestors') has OMEGA_TRAINED iterations behind it.  The weight itself is not clamped at the start: the band
+    binds at the first restart's update."""
     if box is None:
         ok, lb, ub, fmask = m.presolve(lbi, ubi)
     else:
@@ -530,14 +572,26 @@ def blocks(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ve
     cost_int, const = m.cost_int, 0.0
     if m.dred:
         cost_int, const, m.lo[m.oD4], m.hi[m.oD4] = m.dred_terms(lb, ub)
-    x = proj_simplex_rows_sorted(np.zeros((m.R, m.N)), mask)
-    x = r32(x)
-    z = np.clip(np.zeros(m.n_int), lb, ub)
-    y = np.zeros(m.n_dual)
-    kz = m.K(x, z)
-    xa, za, ya, kza = x.copy(), z.copy(), y.copy(), kz.copy()
     omega, eta = (m.omega0 if omega0 is None else float(omega0)), (m.eta if eta is None else float(eta))
     om_lo, om_hi = omega * 1e-5, omega * 1e5
+    if start is None:
+        x = proj_simplex_rows_sorted(np.zeros((m.R, m.N)), mask)
+        x = r32(x)
+        z = np.clip(np.zeros(m.n_int), lb, ub)
+        y = np.zeros(m.n_dual)
+    else:
+        x0, z0, y0, omega = r32(np.asarray(start[0], float)), start[1], start[2], float(start[3])
+        x, theta = proj_simplex_rows_sorted(x0, mask, return_theta=True)
+        if fp32:                                         # (an fp32 threshold, as on every pass but the certificate's)
+            x = _f32(np.where(mask, np.maximum(x0 - _theta32(x0, mask, theta)[:, None], 0), 0.0))
+        z = np.clip(np.array(z0, float), lb, ub)
+        y = np.array(y0, float)
+        if warm_band[0] > 0:
+            om_lo = min(omega * warm_band[0], om_hi)
+        if warm_band[1] > 0 and lineage >= OMEGA_TRAINED:
+            om_hi = max(omega * warm_band[1], om_lo)
+    kz = m.K(x, z)
+    xa, za, ya, kza = x.copy(), z.copy(), y.copy(), kz.copy()
     k = k_since = 0
     ks_base = -ce
     restart_pending = False
@@ -570,7 +624,7 @@ def blocks(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ve
                 vv = (x.astype(f4) - f4(tau) * g).astype(np.float64)
                 xn, theta = proj_simplex_rows_sorted(vv, mask, return_theta=True)
                 if not check:       # (plain iterations: an fp32 threshold; certificate ones refine it in fp64)
-                    xn = np.where(mask, np.maximum(vv - _f32(theta)[:, None], 0), 0.0)
+                    xn = np.where(mask, np.maximum(vv - _theta32(vv, mask, theta)[:, None], 0), 0.0)
                 xn = _f32(xn)
             else:
                 xn = proj_simplex_rows_sorted(x - tau * rcx, mask)
@@ -579,11 +633,13 @@ def blocks(m, lbi=None, ubi=None, tol=1e-7, max_iters=100000, check_every=64, ve
             if fp32 and not check:
                 # outside certificate iterations the column sums S (C1/C2) and the per-function CPU sums (C5, times
                 # cpr) are fp32 accumulators
-                Sx, Ux = m.colsum(m.row_m[:, None] * xn), m.colsum(m.row_w[:, None] * xn)
-                dS = (_f32(Sx) - Sx).ravel()
+                # (added row by row in float32, colsum32: over the ~N rows of a function with workload everywhere the
+                # error reaches several ulps, which one rounding of the fp64 sum does not show)
+                dS = (m.colsum32(m.row_m[:, None] * xn) - m.colsum(m.row_m[:, None] * xn)).ravel()
+                Ux = m.colsum32(m.row_w[:, None] * xn)
                 act[m.o1:m.o1 + FN] += dS
                 act[m.o2:m.o2 + FN] += dS
-                act[m.o5:m.o5 + m.N] += _f32(_f32(Ux) * m.cpr32).sum(axis=0) - (m.wc * xn).sum(axis=0)
+                act[m.o5:m.o5 + m.N] += _f32(Ux * m.cpr32).sum(axis=0) - (m.wc * xn).sum(axis=0)
             s = sig * m.rho ** 2
             V = y - s * (m.K(2 * xn - x, 2 * zn - z) if inline_reflect else 2 * act - kz)
             with np.errstate(invalid="ignore"):
